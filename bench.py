@@ -3,7 +3,19 @@
 training images/sec, pix2pix 256x256 bs16 per GPU, 1/2/4/8 GPUs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model pix2pix|srgan|fsrgan|autoencoder]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it builds the model,
+warms up, times the K steps, writes the outputs (--dump-outputs) and prints
+the result line.  `--full` adds every secondary leg listed under "Extra
+fields" below (graph-vs-eager check, roofline and live traffic, the
+content-free and bf16x6 twin measurements, the CPU baseline); without it those
+fields are null.  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (float32): `losses`, `gen_output` (G(x)), and a
+fixed seeded sample of both networks' updated parameters (`g_params`,
+`d_params`).  The inputs and the initial weights are seeded, so two runs with
+the same arguments are comparable output for output.
 
 Workloads (one "step" = the reference's train_step on one synthetic batch
 already resident in HBM, per GPU):
@@ -27,7 +39,11 @@ math, bf16x6 (fp32 operands split exactly into three bf16 pieces, the six
 significant piece products accumulated in fp32 -- fp32-accurate, see
 DESIGN.md); DG_CONV_MATH=fp32 selects the exact-fp32 MFMA path.
 
-Prints ONE JSON line (rank 0).  Extra fields:
+Prints ONE JSON line (rank 0).  Extra fields (--full only):
+  graph_equals_eager  one eager step and one replay of the captured graph from
+                the same snapshot end bit-identical (N=1: a difference ends the run)
+  core, fp32_exact    pix2pix, N=1: the same step without the VGG19 content
+                term / with every fp16x3 GEMM on bf16x6, timed like the headline
   roofline      conv engine (the dominant kernels): algorithmic conv FLOPs of
                 one step / summed conv launch time measured with HIP events on
                 the launching stream, vs the peak of the conv math in use
@@ -120,7 +136,14 @@ def main():
     ap.add_argument("--no-twin", action="store_true",
                     help="pix2pix: skip the bf16x6 twin measurement (fp32_exact: every conv GEMM on six bf16 "
                          "piece products instead of fp16x3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: graph-vs-eager check, roofline + live traffic, the core and "
+                         "bf16x6 twin measurements, the CPU baseline (each still has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    # a plain run measures the headline only: every secondary leg below is gated on `lean`
+    lean = args.profile_only or not args.full
     wl = WORKLOADS[args.model]
     batch = args.batch or wl["batch"]
     fp16 = bool(wl.get("fp16", 0) if args.fp16 is None else args.fp16) and args.model != "pix2pix"
@@ -248,7 +271,7 @@ def main():
         # (--profile-only: the check's snapshot copies and comparisons would land in the profiled
         # window as non-step kernels -- at::native compares, rocclr copies -- so it runs only in
         # the measured bench)
-        if graph is not None and not args.profile_only:
+        if graph is not None and not lean:
             check = graph_vs_eager(trainer, graph, x, y, strict=world == 1)
 
         def step():
@@ -291,6 +314,8 @@ def main():
         from dgan import nets as _nets
         conv_math = f"G/D {_nets.P2P_MATH}, VGG19 {os.environ.get('DG_VGG_MATH', 'f16x3')}"
     losses = trainer.loss.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, losses)
     ms_per_step = elapsed / args.steps * 1e3
     images = world * batch * args.steps
     value = images / elapsed
@@ -298,7 +323,7 @@ def main():
     # ---- roofline of the conv engine (HIP events, eager pass) ---------------
     roofline = None
     step_flops = None
-    if not args.profile_only:
+    if not lean:
         with ops.ConvProfile() as prof:
             trainer.step(x, y)
         torch.cuda.synchronize()
@@ -359,7 +384,7 @@ def main():
                 print(json.dumps({**r, "tflops": r["flops"] / (r["ms"] * 1e-3) / 1e12}), file=sys.stderr)
 
     core = None
-    if args.model == "pix2pix" and content and world == 1 and not args.no_core and not args.profile_only:
+    if args.model == "pix2pix" and content and world == 1 and not args.no_core and not lean:
         del model, trainer, graph
         torch.cuda.empty_cache()
         _, _, _, el_core = measure(False)
@@ -367,7 +392,7 @@ def main():
                 "workload": "the same step without the VGG19 content term (pix2pix.py:87 weight 0)"}
 
     twin = None
-    if (args.model == "pix2pix" and world == 1 and not args.no_twin and not args.profile_only
+    if (args.model == "pix2pix" and world == 1 and not args.no_twin and not lean
             and os.environ.get("DG_P2P_MATH", "f16x3") == "f16x3"):
         torch.cuda.empty_cache()
         _, _, _, el_twin = measure(content, twin=True)
@@ -378,7 +403,7 @@ def main():
 
     # ---- CPU baseline: torch fp32 restatement, rank 0, N=1 only -------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and not lean:
         cpu = cpu_baseline(args, wl, batch, content)
 
     if rank == 0:
@@ -426,6 +451,28 @@ def main():
         print(json.dumps(out), file=json_out, flush=True)
     if distributed:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of a tensor too large to write whole
+DUMP_WHOLE_BYTES = 16 << 20    # tensors up to this size are written whole (three of them: < 64 MB)
+
+
+def dump_outputs(out_dir, trainer, losses):
+    """What a caller of the timed step holds after the last one, as out_dir/<name>.npy (float32):
+    the loss vector the step returns, G(x) (trainer.gen_output) and both networks' updated
+    parameters.  A tensor above DUMP_WHOLE_BYTES is written as DUMP_SAMPLE of its elements at
+    fixed seeded positions (the same positions in every run and build)."""
+    from dgan.trainer import state_tensors
+    os.makedirs(out_dir, exist_ok=True)
+    st = state_tensors(trainer)
+    tensors = {"gen_output": trainer.gen_output, "g_params": st["G.data"], "d_params": st["D.data"]}
+    np.save(os.path.join(out_dir, "losses.npy"), np.asarray(losses, dtype=np.float32))
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.numel() * 4 > DUMP_WHOLE_BYTES:
+            idx = np.sort(np.random.default_rng(20240917).integers(0, t.numel(), size=DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def graph_vs_eager(trainer, graph, x, y, strict=True):

@@ -3,7 +3,10 @@
 from bench lines whose traffic was measured live (two rocprofv3 --pmc child runs of the same
 workload, bench.py pmc_leg), stamped with this tree's csrc_sha and the commit.
 
-    python scripts/traffic_from_bench.py LABEL COMMIT gpurun_out/<tag>_bench*.json
+    python scripts/traffic_from_bench.py LABEL COMMIT <bench line>.json ...
+
+Each file holds the result line of a `python bench.py --full [--model M]` run (a plain run does
+not measure the traffic).
 """
 import json
 import os
