@@ -143,6 +143,9 @@ _SIGS = {
     "dg_gan_loss_workspace_size": (c_int, [ctypes.POINTER(c_size_t)]),
     "dg_gan_loss": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_int, ctypes.POINTER(c_float),
                             _P, _P, _P, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "dg_bn_fold": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P]),
+    "dg_u8_stage": (c_int, [c_int] * 12 + [_P, _P, _P]),
+    "dg_u8_unstage": (c_int, [c_int] * 13 + [_P, _P, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

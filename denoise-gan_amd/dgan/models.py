@@ -139,6 +139,12 @@ class Generator(Network):
                      step_dev=self.arena.iterations)
         return out
 
+    def predict(self, x, batch_size=None):
+        """Keras `model.predict` (infer.py:60): numpy [N,H,W,3] in [-1, 1] -> numpy, through the
+        BN-folded inference path (dgan/infer.py), refolded from the current weights on every call."""
+        from .infer import predict
+        return predict(self, x, batch_size)
+
 
 class Discriminator(Network):
     """PatchGAN discriminator (pix2pix.py:194-220); called as D([inp, tar])."""

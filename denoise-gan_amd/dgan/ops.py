@@ -1040,3 +1040,48 @@ def gan_loss(gen, tgt, logit_real, logit_fake, out, coef, content=None, dgen=Non
          pix_ld(dgen, C) if dgen is not None else C, _p(dlogit_real_d), _p(dlogit_fake_d), _p(dlogit_fake_g), _p(buf),
          n, _stream())
     return out
+
+
+PAD = {"black": 0, "reflect": 1}   # include/dgan.h DG_PAD_*
+
+
+def bn_fold(w, gamma, beta, moving_mean, moving_var, w_out, bias_out, transpose=False, eps=1e-3, bias_in=None):
+    """BatchNorm (moving statistics) folded into the preceding conv (dg_bn_fold): w a dense Conv2D
+    kernel [kh,kw,Cin,Cout] or, transpose, a Conv2DTranspose kernel [kh,kw,Cout,Cin]."""
+    kh, kw, a, b = w.shape
+    Cin, Cout = (b, a) if transpose else (a, b)
+    for t in (w, w_out):
+        if not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda:
+            raise DGError("bn_fold: dense fp32 device kernels")
+    if w_out.numel() != w.numel() or any(t.numel() != Cout for t in (gamma, beta, moving_mean, moving_var, bias_out)):
+        raise DGError("bn_fold: shapes do not match the kernel")
+    call("dg_bn_fold", kh * kw, Cin, Cout, int(bool(transpose)), _p(w), _p(gamma), _p(beta), _p(moving_mean),
+         _p(moving_var), float(eps), _p(bias_in), _p(w_out), _p(bias_out), _stream())
+    return w_out, bias_out
+
+
+def _u8_args(t, shape, dtype, what):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise DGError(f"{what}: expected a dense {dtype} device tensor of shape {tuple(shape)}, got "
+                      f"{t.dtype} {tuple(t.shape)}")
+
+
+def u8_stage(img, tiles, g, pad="black"):
+    """uint8 images [n,h,w,3] -> fp32 tiles [n*gi*gj,Th,Tw,3] in [-1, 1] (dg_u8_stage); g: a
+    dgan.infer.TileGeometry."""
+    n = img.shape[0]
+    _u8_args(img, (n, g.h, g.w, 3), torch.uint8, "u8_stage input")
+    _u8_args(tiles, (n * g.gi * g.gj, g.Th, g.Tw, 3), torch.float32, "u8_stage tiles")
+    call("dg_u8_stage", n, g.h, g.w, g.Th, g.Tw, g.Sh, g.Sw, g.oy, g.ox, g.gi, g.gj, PAD[pad], _p(img), _p(tiles),
+         _stream())
+    return tiles
+
+
+def u8_unstage(tiles, out, g):
+    """fp32 tiles -> uint8 images [n,h,w,3], each pixel from its one tile's interior (dg_u8_unstage)."""
+    n = out.shape[0]
+    _u8_args(out, (n, g.h, g.w, 3), torch.uint8, "u8_unstage output")
+    _u8_args(tiles, (n * g.gi * g.gj, g.Th, g.Tw, 3), torch.float32, "u8_unstage tiles")
+    call("dg_u8_unstage", n, g.h, g.w, g.Th, g.Tw, g.Sh, g.Sw, g.oy, g.ox, g.gi, g.gj, g.mt, g.ml, _p(tiles), _p(out),
+         _stream())
+    return out

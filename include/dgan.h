@@ -581,6 +581,37 @@ int dg_gan_loss(int B, int H, int W, int C, const float *gen, int ldgen, const f
                 float *dlogit_real_d, float *dlogit_fake_d, float *dlogit_fake_g,
                 void *ws, size_t ws_bytes, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Image inference (the reference's infer.py:40-68 / infer_video.py:138-159): BatchNorm with
+ * moving statistics is a per-channel affine with constant coefficients, so it folds into the
+ * preceding conv, and the uint8 <-> [-1, 1] conversions run on the device around the tiles the
+ * generator reads.
+ * ---------------------------------------------------------------------- */
+/* One layer's fold, fp32: s[c] = gamma[c] / sqrt(moving_var[c] + eps); w_out = w * s[co];
+ * bias_out[c] = beta[c] + (bias_in[c] - moving_mean[c]) * s[c] (bias_in may be NULL = 0).
+ * w is a Conv2D kernel [taps][Cin][Cout] (co the last axis) or, transpose != 0, a
+ * Conv2DTranspose kernel [taps][Cout][Cin] (co axis 1); taps = kh*kw.  w_out may not alias w. */
+int dg_bn_fold(int taps, int Cin, int Cout, int transpose, const float *w, const float *gamma, const float *beta,
+               const float *moving_mean, const float *moving_var, float eps, const float *bias_in, float *w_out,
+               float *bias_out, dg_stream_t stream);
+/* uint8 images [n][h][w][3] (dense, device) -> fp32 tiles [n*gi*gj][Th][Tw][3], tile (i, j) of
+ * image m at index (m*gi + i)*gj + j.  Row ty of tile (i, j) reads image row r = oy + i*Sh + ty,
+ * column tx reads c = ox + j*Sw + tx.  Inside the image the value is
+ * (float(u8) * (1.0f/255.0f)) * 2.0f - 1.0f; outside, DG_PAD_BLACK gives -1 (a zero pad before
+ * the * 2 - 1) and DG_PAD_REFLECT reads index j = r mod p, j >= h ? p - j : j with p = 2(h - 1)
+ * (0 when h == 1): numpy's pad mode "reflect" for any pad width. */
+enum { DG_PAD_BLACK = 0, DG_PAD_REFLECT = 1 };
+int dg_u8_stage(int n, int h, int w, int Th, int Tw, int Sh, int Sw, int oy, int ox, int gi, int gj, int pad,
+                const unsigned char *img, float *tiles, dg_stream_t stream);
+/* The inverse gather: output pixel (y, x) of [n][h][w][3] uint8 takes tile row y - (oy + i*Sh) of
+ * tile i = clamp((y - oy - margin_top) / Sh, 0, gi - 1) (columns alike): the one tile whose
+ * interior [margin, margin + S) holds it.  Value uint8(floor(clamp(v*0.5f + 0.5f, 0, 1) * 255.0f + 0.5f))
+ * (round to nearest: with the reference's truncation the two conversions would not invert each
+ * other), NaN -> 0.  DG_ERR_ARG unless every pixel reads inside its tile (margin >= 0, margin + S <= T,
+ * oy + margin_top <= 0, and the last tile reaches the last row / column). */
+int dg_u8_unstage(int n, int h, int w, int Th, int Tw, int Sh, int Sw, int oy, int ox, int gi, int gj, int margin_top,
+                  int margin_left, const float *tiles, unsigned char *out, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
