@@ -21,7 +21,8 @@
 // staged global -> registers -> LDS (double buffered, one barrier per
 // K-tile), stored k-major ([k][m], [k][n]) so every MFMA operand fetch is a
 // conflict-free ds_read_b32 of 32 consecutive floats per half-wave.
-#include "conv_impl.h"
+#include "conv_plan.h"
+#include "conv_tiles.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -644,8 +645,7 @@ k_narrow_dgrad(const GemmArgs p, int w_in_lds) {
 // per-lane ds_read_b128 are conflict-free) and the chunk's weights of the
 // phase's TH x TW taps (read as LDS broadcasts), then runs fp32 FMA chains.
 // dy is read from HBM once (the GEMM recast writes and re-reads a
-// pixels x (taps*Ci) matrix instead).
-constexpr int DIR_PH = 8, DIR_PW = 32, DIR_CC = 32, DIR_CS = DIR_CC + 4;
+// pixels x (taps*Ci) matrix instead).  (DIR_*: conv_plan.h, with direct_dgrad_ok)
 
 template <int CI, int TH, int TW>
 __global__ void __launch_bounds__(256)
@@ -747,17 +747,7 @@ k_direct_dgrad(const GemmArgs p, int tiles_x, int tiles_y) {
     }
 }
 
-// direct DGRAD kernels instantiated: (Ci, taps per phase) of the layers above
-// (measured per layer in the training step: VGG block1_conv1 dgrad 0.210 ->
-// 0.172 ms (0.132 with the batched, prefetched halo loads), D.down1 dgrad
-// 0.208 -> 0.122 ms; G.last forward with Co 128 ran 0.239 -> 0.38 ms, so
-// Co > 64 stays on the GEMM recast)
-static bool direct_dgrad_ok(const ConvGeom &g) {
-    if (g.Co % DIR_CC || g.Co > 64) return false;
-    const bool t33 = g.Th == 3 && g.Tw == 3, t22 = g.Th == 2 && g.Tw == 2;
-    return (g.Ci == 3 && (t33 || t22)) || (g.Ci == 6 && t22);
-}
-
+// the direct DGRAD kernels instantiated: direct_dgrad_ok (conv_plan.h)
 static void launch_direct_dgrad(const GemmArgs &a, hipStream_t s) {
     const ConvGeom &g = a.g;
     const int Hp = (g.H + g.sh - 1) / g.sh, Wp = (g.W + g.sw - 1) / g.sw;
@@ -920,19 +910,7 @@ k_narrow_wgrad(const GemmArgs p) {
 // each lane a chain of 4 pixels' loads in flight -- took 1.04 ms for
 // FastSRGAN's output conv at bs8; the 3 -> 32 input conv's filter gradient ran
 // 455 us per call on 64 x 64 fp32 tiles, 27 of whose 64 rows exist.)
-constexpr int NWT_TP = 64;
-constexpr int NWT_QMAX = 4;    // slots per thread: Q * CG <= 1024
-static int narrow_tile_groups(const ConvGeom &g) { return (g.Co + 3) / 4; }
-static size_t narrow_tile_lds(const ConvGeom &g) {
-    return ((size_t)g.kh * (NWT_TP + g.kw - 1) * g.Ci + 4 * NWT_TP * (size_t)narrow_tile_groups(g)) * sizeof(float);
-}
-static bool narrow_tile_ok(const ConvGeom &g) {
-    const long S = (long)g.kh * g.kw * g.Ci * narrow_tile_groups(g);
-    return g.sh == 1 && g.sw == 1 && S <= 256L * NWT_QMAX && narrow_tile_lds(g) <= 64 * 1024;
-}
-static int narrow_tile_segments(const ConvGeom &g) {
-    return g.N * g.Ho * ((g.Wo + NWT_TP - 1) / NWT_TP);
-}
+// (NWT_TP, NWT_QMAX and the narrow_tile_* geometry: conv_plan.h)
 
 __global__ void __launch_bounds__(256)
 k_narrow_wgrad_tile(const GemmArgs p, int nseg, float *__restrict__ part) {
@@ -1207,607 +1185,20 @@ k_recast_wgrad_gather(const GemmArgs p, const float *__restrict__ dy, int lddy, 
 }
 
 // -------------------------------------------------------------------------
-// Host side: descriptor, planner, launch
+// Host side: launch (the descriptor and the planner: conv_plan.h, conv_plan.hip)
 // -------------------------------------------------------------------------
-// tile configs: block tile, wave grid, K-tile depth, min waves/SIMD (register budget),
-// resident blocks per CU (LDS / registers), relative cost per FLOP (measured on MI355X)
-struct TileCfg {
-    int bm, bn, wgm, wgn, bk, minw, bpc;
-    double eff;
-};
-static const TileCfg kCfgs[] = {
-    {128, 128, 2, 2, 32, 2, 2, 1.00}, {128, 64, 2, 2, 32, 2, 2, 1.12}, {64, 128, 2, 2, 32, 2, 2, 1.12},
-    {64, 64, 2, 2, 32, 2, 3, 1.35},   {32, 128, 1, 4, 32, 2, 3, 1.50}, {128, 128, 2, 2, 16, 3, 3, 1.00},
-    {128, 64, 2, 2, 16, 3, 3, 1.12},
-    // 32-wide tiles for the 32-channel layers of the SR discriminators (srgan.py:232-272):
-    // a 64-wide tile computes half zeros there
-    {128, 32, 4, 1, 32, 2, 3, 1.40}, {256, 32, 4, 1, 32, 2, 2, 1.30},
-};
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-// bf16x6 kernel configs (conv_x6.hip launch_gemm_x6), K-tile 16
-static const TileCfg kX6Cfgs[] = {
-    {128, 128, 2, 2, 16, 2, 2, 1.00}, {128, 64, 2, 2, 16, 2, 2, 1.15}, {64, 128, 2, 2, 16, 2, 2, 1.15},
-    {64, 64, 2, 2, 16, 3, 4, 1.40},   {256, 128, 4, 2, 16, 2, 1, 1.00}, {128, 256, 2, 4, 16, 2, 1, 0.90},
-    {128, 32, 4, 1, 16, 3, 4, 1.45},   // 32-wide (SR discriminators' 32-channel layers)
-};
-constexpr int kNumX6Cfgs = sizeof(kX6Cfgs) / sizeof(kX6Cfgs[0]);
-// fp16 kernel configs (conv_x6.hip launch_gemm_f16: the same tiles, K-tile 32)
-static const TileCfg kF16Cfgs[] = {
-    {128, 128, 2, 2, 32, 2, 2, 1.00}, {128, 64, 2, 2, 32, 2, 2, 1.15}, {64, 128, 2, 2, 32, 2, 2, 1.15},
-    {64, 64, 2, 2, 32, 3, 4, 1.40},   {256, 128, 4, 2, 32, 2, 1, 1.00}, {128, 256, 2, 4, 32, 2, 1, 0.90},
-    {128, 32, 4, 1, 32, 3, 4, 1.45},   // 32-wide (SR discriminators' 32-channel layers)
-};
-constexpr int kNumF16Cfgs = sizeof(kF16Cfgs) / sizeof(kF16Cfgs[0]);
-// fp16x3 kernel configs (conv_x6.hip launch_gemm_x3: four images per K-tile of 32, the
-// 128-wide tiles one K-tile ahead in two LDS buffers)
-static const TileCfg kX3Cfgs[] = {
-    {128, 128, 2, 2, 32, 2, 2, 1.00}, {128, 64, 2, 2, 32, 2, 3, 1.15}, {64, 128, 2, 2, 32, 2, 3, 1.15},
-    {64, 64, 2, 2, 32, 3, 3, 1.40},   {256, 128, 4, 2, 32, 2, 1, 1.00}, {128, 256, 2, 4, 32, 2, 1, 0.90},
-    {128, 32, 4, 1, 32, 3, 2, 1.45},
-};
-constexpr int kNumX3Cfgs = sizeof(kX3Cfgs) / sizeof(kX3Cfgs[0]);
-
-struct OpPlan {
-    int narrow;      // 1 => VALU narrow kernel
-    int direct;      // narrow DGRAD on k_direct_dgrad (dy halo staged in LDS)
-    int x6;          // 1 => bf16x6 split-precision kernel (kX6Cfgs), 2 => fp16 (kF16Cfgs), 3 => fp16x3 halo
-                     // forward (DG_MATH_F16X3), else fp32 MFMA (kCfgs)
-    int cfg;         // tile config index
-    int vec;
-    int splits, kchunk;
-    int M, N, K, nphase;
-    int mtiles, ntiles;
-    size_t slab_bytes;  // split-K partial slabs
-    size_t gemm_bytes;  // workspace of the GEMM (split-K slabs + bf16x6 planes)
-    size_t ws_bytes;    // total workspace of the layer op (GEMM + bias partials)
-    size_t colsum_off;  // bwd_filter: offset of the bias column-sum partials
-    // bf16x6: operand plane dims (rows x C for A and B) and workspace offsets
-    long x6_ra, x6_rb;
-    int x6_ca, x6_cb;
-    size_t x6_a_off, x6_b_off;
-    // halo-tiled bf16x6 kernel (conv_x6h.hip): 1 = stride-1 3x3 FWD / DGRAD,
-    // 2 = stride-2 4x4 DGRAD phases; cfg = its BN, tiles of hph x 16 output pixels
-    // (hph 8, or 16: the fp16x3 3x3 16 x 16 patch on 8 waves)
-    int halo, htx, hty, hph;
-    // fp16x3 halo plans without split-K: patches per block (persistent blocks, conv_x6h.hip)
-    int ptiles;
-    // small-Cin 4x4 stride-2 kernels (conv_small.hip); WGRAD: conv-view output rows per block
-    int small, small_rows;
-    // single-output-channel direct kernels (conv_co1.hip)
-    int co1;
-    // ConvT(3) forward on the fused MFMA + col2im kernel (conv_tlast.hip)
-    int tlast;
-    // narrow stride-1 filter gradient on row segments (k_narrow_wgrad_tile): partial blocks
-    int ntile;
-    // fp16x3 input gradient: workspace offset of the max |dy| float (no scale source set)
-    size_t x3_max_off;   // (+X3_SLOT floats: max |x| when the x operand has no scale source)
-};
-
-// A narrow op (GEMM N <= 8) recast as a 1x1-geometry MFMA GEMM plus a gather:
-//   FWD,   Co == 1 : V[p_in][(i,j)]      = x[p_in][:] . w[(i,j)][:]   ; y = shift-and-add of V
-//   DGRAD, Ci <= 8 : V[p_out][(i,j,ci)]  = dy[p_out][:] . w[(i,j,ci)][:] ; dx = col2im(V)
-//   WGRAD, Co == 1 : dw[(i,j)][ci]       = sum_p G[p][(i,j)] x[p][ci], G = dy gathered per tap
-struct Recast {
-    int on;
-    int mode1;          // engine mode of the 1x1 GEMM
-    ConvGeom g1;        // its geometry (N=1, H=1, W=pixels)
-    OpPlan p1;          // its plan
-    int nv;             // columns of V / G
-    int nvp;            // row stride of V (nv rounded up so the 1x1 GEMM stays on the bf16x6 path)
-    size_t wt_off, v_off, slab_off, bytes;
-};
-
-}  // namespace dg
-
-struct dg_conv_desc_s {
-    int transpose;
-    int math;                        // DG_MATH_*
-    // fp16x3 input gradient scale context (dg_conv_set_grad_scale): sources (m, g) of the dy
-    // and dx planes' scales, and where max |dx| goes (device pointers; NULL = unset)
-    const float *gs_dy_m, *gs_dy_g, *gs_dx_m, *gs_dx_g;
-    float *gs_dx_max;
-    // fp16x3 activation scale context (dg_conv_set_act_scale): source (m, g, c) of the x planes'
-    // scale, of the forward's output planes' scale, and where max |y| of the forward goes
-    const float *as_x_m, *as_x_g, *as_x_c, *as_y_m, *as_y_g, *as_y_c;
-    float *as_y_max;
-    int N, H, W, Cin, Cout, Ho, Wo;  // layer view
-    dg::ConvGeom g;                  // conv view
-    dg::OpPlan plan[3];              // indexed by DG_OP_*
-    dg::Recast rc[3];
-};
-
-namespace dg {
-
-static int engine_mode(const dg_conv_desc_s *d, int op) {
-    // layer op -> conv-view engine
-    if (!d->transpose) return op == DG_OP_FWD ? MODE_FWD : (op == DG_OP_BWD_DATA ? MODE_DGRAD : MODE_WGRAD);
-    return op == DG_OP_FWD ? MODE_DGRAD : (op == DG_OP_BWD_DATA ? MODE_FWD : MODE_WGRAD);
-}
-
-static bool cfg_vec(const ConvGeom &g, int mode, int bk) {
-    if (mode == MODE_FWD) return g.Ci % bk == 0;
-    if (mode == MODE_DGRAD) return g.Co % bk == 0;
-    return g.Ci % 4 == 0;
-}
-
-// Tile config + split-K count for plan pl (M, N, K, nphase set) from a config
-// table; returns the modelled time.  Modelled time of a candidate:
-//   rounds x (blocks per CU x per-block MFMA work) / (CU peak x occupancy efficiency)
-// + split-K slab traffic, where blocks per CU = min(resident limit, blocks / 256).
-// Plan features switched off for same-box A/B runs: DG_PLAN_DISABLE is a
-// comma-separated list of {shortk, small, co1, tlast, direct, halo, halo2, halo4, halo_f16, xcd_phase, narrow_px, ntile,
-// tile32, f16planes, halo32}
-// (read when a descriptor is planned; unset in production runs)
-static bool plan_off(const char *feature) {
-    const char *list = getenv("DG_PLAN_DISABLE");
-    if (!list) return false;
-    const size_t n = strlen(feature);
-    for (const char *q = list; *q;) {
-        const char *e = strchr(q, ',');
-        const size_t len = e ? (size_t)(e - q) : strlen(q);
-        if (len == n && !strncmp(q, feature, n)) return true;
-        if (!e) break;
-        q = e + 1;
-    }
-    return false;
-}
-
-static double choose_tiles(OpPlan &pl, const TileCfg *cfgs, int ncfg, double peak, const char *force_env,
-                           int rule = -1) {
-    const double cu_flops = peak / 256.0;
-    static const double occ_eff[] = {0.0, 0.62, 0.80, 0.88, 0.92};
-    int forced = rule;   // (a measured per-shape rule of the caller; the environment overrides it)
-    if (const char *f = getenv(force_env)) forced = atoi(f);
-    // DG_FORCE_SPLITS: split-K count for sweeps (scripts/diag/deep_sweep.py); unset in production
-    long fsplits = 0;
-    if (const char *f = getenv("DG_FORCE_SPLITS")) fsplits = atol(f);
-    // fp32 GEMMs with a short K over many rows (the Cin 3/6 layers and the
-    // G.last recast: K 27..128, M >= 64K): per-layer sweep on MI355X (bs32)
-    // has the 128x64 BK-16 three-blocks-per-CU tile fastest on every one
-    // (D.down1 fwd 0.159 -> 0.117 ms, G.last bwd_data 0.188 -> 0.166, G.last
-    // recast 0.241 -> 0.219); the MFMA-time model misses their prologue /
-    // epilogue weight
-    if (forced < 0 && cfgs == kCfgs && pl.K <= 256 && pl.N <= 128 && (long)pl.M * pl.nphase >= 65536 &&
-        !plan_off("shortk"))
-        forced = (pl.N <= 32 && !plan_off("tile32")) ? 7 : 6;   // (32 columns: the 128 x 32 tile)
-    int best = -1; double best_t = 1e30; long best_splits = 1;
-    for (int c = 0; c < ncfg; ++c) {
-        const TileCfg &t = cfgs[c];
-        if (forced >= 0 && c != forced) continue;
-        if (forced < 0 && pl.N <= 64 && t.bn > 64) continue;
-        if (forced < 0 && t.bn == 32 && plan_off("tile32")) continue;
-        long mt = (pl.M + t.bm - 1) / t.bm, nt = (pl.N + t.bn - 1) / t.bn;
-        long tiles = mt * nt * pl.nphase;
-        long ktiles = (pl.K + t.bk - 1) / t.bk;
-        for (long splits = 1; splits <= std::max<long>(1, fsplits > 0 ? ktiles : ktiles / 4); splits *= 2) {
-            if (fsplits > 0 && splits != fsplits) continue;
-            long kt_per = (ktiles + splits - 1) / splits;
-            long blocks = tiles * splits;
-            long bpc = std::min<long>(t.bpc, (blocks + 255) / 256);
-            double rounds = std::ceil((double)blocks / (256.0 * bpc));
-            // occupancy in 4-wave units: an 8-wave block counts as two
-            const long occ = std::min<long>(4, bpc * (t.wgm * t.wgn) / 4);
-            const double eff = t.eff;
-            double tc = rounds * bpc * 2.0 * t.bm * t.bn * kt_per * t.bk * eff / (cu_flops * occ_eff[occ]);
-            double ts = splits > 1 ? (double)splits * pl.nphase * pl.M * pl.N * 8.0 / 5.0e12 + 2e-6 : 0.0;
-            if (tc + ts < best_t) { best_t = tc + ts; best = c; best_splits = splits; }
-            if (blocks >= 1024 && fsplits <= 0) break;
-        }
-    }
-    if (best < 0) best = 0;
-    pl.cfg = best;
-
-    const TileCfg &t = cfgs[best];
-    long ktiles = (pl.K + t.bk - 1) / t.bk;
-    long kt_per = (ktiles + best_splits - 1) / best_splits;
-    pl.kchunk = (int)(kt_per * t.bk);
-    pl.splits = (int)((ktiles + kt_per - 1) / kt_per);
-    pl.mtiles = (pl.M + t.bm - 1) / t.bm;
-    pl.ntiles = (pl.N + t.bn - 1) / t.bn;
-    return best_t;
-}
-
-// x6_extra: seconds the split-precision path costs beyond its GEMM and split passes (plan_all:
-// a filter gradient whose operands no other op of the layer splits measures and splits both)
-static OpPlan make_plan(const ConvGeom &g, int mode, int math, double x6_extra = 0.0) {
-    OpPlan pl{};
-    if (mode == MODE_FWD) {
-        pl.M = g.N * g.Ho * g.Wo; pl.N = g.Co; pl.K = g.kh * g.kw * g.Ci; pl.nphase = 1;
-        pl.narrow = g.Co < 8;
-    } else if (mode == MODE_DGRAD) {
-        pl.nphase = g.sh * g.sw;
-        int Hp = (g.H + g.sh - 1) / g.sh, Wp = (g.W + g.sw - 1) / g.sw;
-        pl.M = g.N * Hp * Wp; pl.N = g.Ci; pl.K = g.Th * g.Tw * g.Co;
-        pl.narrow = g.Ci < 8;
-    } else {
-        pl.M = g.kh * g.kw * g.Ci; pl.N = g.Co; pl.K = g.N * g.Ho * g.Wo; pl.nphase = 1;
-        pl.narrow = g.Co < 8;
-    }
-    pl.vec = cfg_vec(g, mode, 32);
-    if (co1_ok(g, mode) && math != DG_MATH_FP16 && !plan_off("co1")) {
-        // Co == 1 (PatchGAN last layer): direct kernels, exact fp32 FMA chains
-        pl.co1 = 1; pl.narrow = 0;
-        pl.splits = 1; pl.kchunk = pl.K; pl.mtiles = pl.ntiles = 1;
-        pl.slab_bytes = mode == MODE_WGRAD ? (size_t)co1_wgrad_blocks(g) * g.kh * g.kw * g.Ci * sizeof(float) : 0;
-        pl.ws_bytes = pl.gemm_bytes = pl.slab_bytes;
-        if (getenv("DG_PLAN_DEBUG"))
-            fprintf(stderr, "[dg plan] mode %d M=%d N=%d K=%d -> co1\n", mode, pl.M, pl.N, pl.K);
-        return pl;
-    }
-    if (pl.narrow) {
-        pl.splits = 1; pl.kchunk = pl.K; pl.ws_bytes = 0; pl.slab_bytes = 0;
-        if (mode == MODE_WGRAD && narrow_tile_ok(g) && !plan_off("ntile")) {
-            pl.ntile = 1;
-            pl.splits = std::min(1024, narrow_tile_segments(g));   // partial blocks
-            pl.slab_bytes = (size_t)pl.splits * pl.M * 4 * narrow_tile_groups(g) * sizeof(float);
-            pl.ws_bytes = pl.slab_bytes;
-        } else if (mode == MODE_WGRAD) {
-            // pixels split so that taps*ci_chunks*splits ~ 1024 blocks
-            long blocks = (long)g.kh * g.kw * ((g.Ci + 255) / 256);
-            int s = (int)std::max<long>(1, std::min<long>(1024 / std::max<long>(blocks, 1), pl.K / 64));
-            pl.splits = std::max(1, s);
-            pl.kchunk = (pl.K + pl.splits - 1) / pl.splits;
-            pl.slab_bytes = (size_t)pl.splits * pl.M * pl.N * sizeof(float);
-            pl.ws_bytes = pl.slab_bytes;
-        }
-        pl.gemm_bytes = pl.ws_bytes;
-        return pl;
-    }
-    if (mode == MODE_WGRAD && g.Ci < 8 && narrow_tile_ok(g) && !plan_off("ntile")) {
-        // 1-7 input channels at stride 1 (the SR discriminators' 3 -> 32 input conv): the
-        // filter-gradient GEMM has Q = kh*kw*Ci <= 63 rows; the row-segment kernel instead
-        pl.ntile = 1;
-        pl.splits = std::min(1024, narrow_tile_segments(g));
-        pl.kchunk = pl.K; pl.mtiles = pl.ntiles = 1;
-        pl.slab_bytes = (size_t)pl.splits * pl.M * 4 * narrow_tile_groups(g) * sizeof(float);
-        pl.ws_bytes = pl.gemm_bytes = pl.slab_bytes;
-        if (getenv("DG_PLAN_DEBUG"))
-            fprintf(stderr, "[dg plan] mode %d M=%d N=%d K=%d -> ntile blocks %d\n", mode, pl.M, pl.N, pl.K, pl.splits);
-        return pl;
-    }
-    if (small_conv_ok(g, mode, 0) && !plan_off("small")) {
-        // 3 / 6 input channels, 4x4 stride 2 (G.down1, D.down1, G.last's gradients): exact fp32
-        // on the 32x32x2 MFMA whatever the math mode (neither low-precision path takes Cin 3 / 6)
-        pl.small = 1;
-        pl.splits = 1; pl.kchunk = pl.K; pl.mtiles = pl.ntiles = 1;
-        if (mode == MODE_WGRAD) {
-            pl.small_rows = small_wgrad_rows_per_block(g);
-            const int rows = g.N * g.Ho;
-            pl.splits = (rows + pl.small_rows - 1) / pl.small_rows;
-        }
-        pl.slab_bytes = pl.splits > 1 ? (size_t)pl.splits * pl.M * pl.N * sizeof(float) : 0;
-        pl.ws_bytes = pl.gemm_bytes = pl.slab_bytes;
-        if (getenv("DG_PLAN_DEBUG"))
-            fprintf(stderr, "[dg plan] mode %d M=%d N=%d K=%d -> small splits %d\n", mode, pl.M, pl.N, pl.K, pl.splits);
-        return pl;
-    }
-    // Tile + split-K choice: the cheaper of the fp32 kernel and (math mode
-    // BF16X6, eligible shapes) the bf16x6 kernel plus its two split passes.
-    double t32 = choose_tiles(pl, kCfgs, kNumCfgs, 157.3e12, "DG_FORCE_CFG");
-    int x6_ok = 0;
-    long ra = 0, ca = 0, rb = 0, cb = 0;
-    if (mode == MODE_FWD) {
-        x6_ok = g.Ci % 16 == 0 && g.Co % 16 == 0;
-        ra = (long)g.N * g.H * g.W; ca = g.Ci; rb = (long)g.kh * g.kw * g.Ci; cb = g.Co;
-    } else if (mode == MODE_DGRAD) {
-        x6_ok = g.Co % 16 == 0;
-        ra = (long)g.N * g.Ho * g.Wo; ca = g.Co; rb = (long)g.kh * g.kw * g.Ci; cb = g.Co;
-    } else {
-        x6_ok = g.Ci % 16 == 0 && g.Co % 16 == 0;
-        ra = (long)g.N * g.H * g.W; ca = g.Ci; rb = (long)g.N * g.Ho * g.Wo; cb = g.Co;
-    }
-    // (the bf16x6 kernel keeps a per-row bitmask of valid taps: at most 32 taps; DG_MATH_F16X3
-    // is bf16x6 wherever its fp16x3 forward does not apply)
-    x6_ok = x6_ok && (math == DG_MATH_BF16X6 || math == DG_MATH_F16X3) && 6.0 * ra * ca < 2.0e9 &&
-            6.0 * rb * cb < 2.0e9 && g.kh * g.kw <= 32;
-    // (DG_MATH_F16X3: the halo kernel's fp16x3 form for 3x3 stride-1 forwards (Cin % 32 == 0,
-    // Cout % 16 == 0, Cout > 32) and input gradients (Cout % 32 == 0 chunks the reduction over
-    // output channels, Cin % 16 == 0 and Cin > 32 the BN 64 / 128 tiles), see hx3 below)
-    const bool x3_geom = math == DG_MATH_F16X3 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
-                         !plan_off("x3") && !plan_off("halo") &&
-                         ((mode == MODE_FWD && g.Ci % 32 == 0 && g.Co % 16 == 0 && g.Co > 32) ||
-                          (mode == MODE_DGRAD && g.Co % 32 == 0 && g.Ci % 16 == 0 && g.Ci > 32 &&
-                           !plan_off("x3dgrad")));
-    // fp16x3 on the implicit-GEMM kernel (conv_x6.hip NI 4) for every other eligible op of a
-    // DG_MATH_F16X3 descriptor: 32-channel chunks of the activation / gradient operand,
-    // 16-column weight groups
-    const bool x3_gen = math == DG_MATH_F16X3 && !plan_off("x3") && !plan_off("x3gen") && g.kh * g.kw <= 32 &&
-                        ((mode == MODE_FWD && g.Ci % 32 == 0 && g.Co % 16 == 0) ||
-                         (mode == MODE_DGRAD && g.Co % 32 == 0 && g.Ci % 16 == 0) ||
-                         (mode == MODE_WGRAD && g.Ci % 32 == 0 && g.Co % 32 == 0));
-    if (x6_ok) {
-        OpPlan p6 = pl;
-        double t6 = choose_tiles(p6, kX6Cfgs, kNumX6Cfgs, 2516.6e12 / 6.0, "DG_FORCE_X6CFG");
-        t6 += (double)(ra * ca + rb * cb) * 10.0 / 4.0e12 + 4e-6 + x6_extra;  // split passes: read 4 B, write 6 B
-        // (the implicit-GEMM fp16x3 ops where the split path beats the fp32 tiles at all: on
-        // pix2pix's deepest layers (M 32..128 rows) the fp32 tiles win; DG_FORCE_X3: every
-        // eligible op, for the kernel tests at small sizes.  The halo kernel's fp16x3 3x3 layers
-        // stay forced: the network picks its math by image size, sr_trainer.VGGNetwork.  Plans
-        // of one network in different arithmetics are safe: the host keeps weight planes per
-        // layout (dg_conv_planes_format / _size), dgan/graph.py, tests/test_mixed_math_gpu.py)
-        if (t6 < t32 || getenv("DG_FORCE_X6CFG") || x3_geom || (x3_gen && getenv("DG_FORCE_X3"))) {
-            pl = p6;
-            pl.x6 = 1;
-            pl.x6_ra = ra; pl.x6_ca = (int)ca; pl.x6_rb = rb; pl.x6_cb = (int)cb;
-        }
-    }
-    if (math == DG_MATH_FP16) {
-        // the reference's mixed_float16 policy: one fp16 plane per operand, K-tiles of 32
-        int ok = 0;
-        if (mode == MODE_FWD) ok = g.Ci % 32 == 0 && g.Co % 16 == 0;
-        else if (mode == MODE_DGRAD) ok = g.Co % 32 == 0;
-        else ok = g.Ci % 16 == 0 && g.Co % 16 == 0;
-        ok = ok && 2.0 * ra * ca < 2.0e9 && 2.0 * rb * cb < 2.0e9 && g.kh * g.kw <= 32;
-        if (ok) {
-            pl.x6 = 0;
-            choose_tiles(pl, kF16Cfgs, kNumF16Cfgs, 2516.6e12, "DG_FORCE_F16CFG");
-            pl.x6 = 2;
-            pl.x6_ra = ra; pl.x6_ca = (int)ca; pl.x6_rb = rb; pl.x6_cb = (int)cb;
-        }
-    }
-    if (!pl.x6) choose_tiles(pl, kCfgs, kNumCfgs, 157.3e12, "DG_FORCE_CFG");
-    // halo-tiled kernel: 3x3 stride-1 FWD / DGRAD (kt 3), and the sub-pixel
-    // phases of a 4x4 stride-2 DGRAD (kt 2: ConvT forwards, down-block input gradients)
-    const bool h33 = (mode == MODE_FWD || mode == MODE_DGRAD) && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 &&
-                     pl.K % 144 == 0;
-    // (phase grids that fill at least 3/4 of their 8 x 16 patches: on the deep
-    // U-Net layers -- 8x8 and smaller phase grids -- the generic tiles win,
-    // e.g. up3's forward 0.086 vs 0.243 ms per step)
-    const int hp2 = (g.H + 1) / 2, wp2 = (g.W + 1) / 2;
-    const bool h22 = mode == MODE_DGRAD && g.kh == 4 && g.kw == 4 && g.sh == 2 && g.sw == 2 && g.Th == 2 &&
-                     g.Tw == 2 && pl.K % 64 == 0 &&
-                     4L * hp2 * wp2 >= 3L * ((hp2 + 7) / 8 * 8) * ((wp2 + 15) / 16 * 16) && !plan_off("halo2");
-    // (stride-1 4x4: the PatchGAN's 512-channel conv, input gradient only: its
-    // forward measured 0.709 vs 0.668 ms on the generic 128 x 256 tiles at bs16 x2,
-    // the input gradient 0.666 vs 0.690)
-    const bool h44 = mode == MODE_DGRAD && g.kh == 4 && g.kw == 4 && g.sh == 1 && g.sw == 1 &&
-                     pl.K % 256 == 0 && !plan_off("halo4");
-    // (fp16: 3x3 only, 32-channel chunks; the forward's pool epilogue stays bf16x6)
-    const bool hf16 = pl.x6 == 2 && h33 && pl.K % 288 == 0 && pl.N % 16 == 0 && !plan_off("halo_f16");
-    // fp16x3 forward (DG_MATH_F16X3): 3x3 stride-1 layers with 32-channel chunks and at
-    // least 48 output columns (BN 64 / 128 tiles) -- VGG19's layers after block1_conv1
-    const bool hx3 = x3_geom && pl.x6 == 1 && h33 && pl.K % 288 == 0 && 4.0 * ra * ca < 2.0e9 &&
-                     4.0 * rb * cb < 2.0e9;
-    // fp16x3 stride-2 4x4 input-gradient phases on the halo kernel (ConvT forwards, down-block
-    // input gradients of G / D) where the implicit-GEMM fp16x3 plan applies (32-channel chunks)
-    const bool hx3p = x3_gen && pl.x6 == 1 && h22 && pl.K % 128 == 0 && 4.0 * ra * ca < 2.0e9 &&
-                      4.0 * rb * cb < 2.0e9 && !plan_off("x3h2");
-    // fp16x3 stride-1 4x4 (the PatchGAN's 512-channel conv, forward and input gradient) on the
-    // halo kernel: 11 x 19 halo, BN 64 (72.4 KB, two blocks per CU) -- full step 982 vs 972 img/s
-    // on the implicit-GEMM fp16x3 tiles (profiles/r5/ab_x3h_kt4.txt; DG_PLAN_DISABLE=x3h4)
-    const bool f44 = mode == MODE_FWD && g.kh == 4 && g.kw == 4 && g.sh == 1 && g.sw == 1;
-    const bool hx3q = x3_gen && pl.x6 == 1 && (h44 || f44) && pl.K % 512 == 0 && 4.0 * ra * ca < 2.0e9 &&
-                      4.0 * rb * cb < 2.0e9 && !plan_off("x3h4");
-    if ((pl.x6 == 1 && (h33 || h22 || h44 || hx3q) || hf16) && !plan_off("halo")) {
-        // each input pixel staged once per channel chunk instead of once per tap
-        const int ntap = h33 ? 9 : (h44 || f44 ? 16 : 4);
-        const int bkc = (pl.x6 == 2 || hx3 || hx3p || hx3q) ? 32 : 16;   // channels per chunk
-        int Hout, Wout;
-        if (mode == MODE_FWD) { Hout = g.Ho; Wout = g.Wo; }
-        else if (h33 || h44) { Hout = g.H; Wout = g.W; }
-        else { Hout = (g.H + 1) / 2; Wout = (g.W + 1) / 2; }   // phase 0's grid, the largest
-        pl.halo = h33 ? 1 : (h44 || f44 ? 4 : 2);
-        // fp16x3 3x3 on 16 x 16 patches (8 waves, one block per CU): the K >= 4096 layers (512
-        // reduction channels: VGG19 block4_conv2-4 forward and input gradient, 4-6 % faster, one
-        // stream) where the grid still fills the chip at one block per CU; the shorter-K layers ran
-        // 2-11 % slower on it (profiles/r6/ab_x3h_ph16.txt).  DG_X3H_PH=8|16 forces,
-        // DG_PLAN_DISABLE=x3h16: 8 x 16 everywhere
-        pl.hph = 8;
-        if (hx3 && Hout >= 16 && pl.K >= 4096 && !plan_off("x3h16")) {
-            const long t16 = (long)g.N * ((Wout + 15) / 16) * ((Hout + 15) / 16) * ((pl.N + 127) / 128);
-            pl.hph = t16 >= 256 ? 16 : 8;
-        }
-        if (hx3)
-            if (const char *e = getenv("DG_X3H_PH")) pl.hph = atoi(e) == 16 && Hout >= 16 ? 16 : 8;
-        pl.htx = (Wout + 15) / 16;
-        pl.hty = (Hout + pl.hph - 1) / pl.hph;
-        // (4x4: BN 128 needs 93 KB of LDS -- one block per CU -- and measured 0.685 vs
-        // 0.666 ms for BN 64, which keeps two)
-        // (32 output columns, 3x3: BN 32 -- the SR family's 32-channel layers; a 64-wide tile
-        // spends half its MFMAs on zero columns there)
-        pl.cfg = pl.N > 64 && !h44 && !f44 ? 128 : (h33 && pl.N <= 32 && !plan_off("halo32") ? 32 : 64);
-        pl.mtiles = g.N * pl.htx * pl.hty;
-        // (same-box A/B of the target: 256 -0.2%, 1024 -0.8% full step vs 512)
-        long target = 512;
-        // (diagnostic: DG_X3_TARGET sets the fp16x3 plans' block target for same-box sweeps)
-        if (hx3 && getenv("DG_X3_TARGET")) target = atol(getenv("DG_X3_TARGET"));
-        // fp16x3 3x3 grids short of the target at BN 128: BN 64 tiles, twice the blocks, instead
-        // of (twice the) split-K, whose partial slabs and reduce launch cost more than the halved
-        // tile -- VGG19 block5 at bs32 0.148 -> 0.140 ms fwd, 0.152 -> 0.142 bwd_data, block4_conv1
-        // bwd_data 0.261 -> 0.255 (profiles/r5/ab_x3h_bn64.txt; DG_PLAN_DISABLE=x3h_bn64: BN 128)
-        if (pl.hph == 16) target /= 2;   // (one block per CU)
-        if (hx3 && pl.cfg == 128 && (long)pl.mtiles * ((pl.N + 127) / 128) * pl.nphase < target &&
-            !plan_off("x3h_bn64"))
-            pl.cfg = 64;
-        pl.ntiles = (pl.N + pl.cfg - 1) / pl.cfg;
-        // split-K over channel chunks (at least two per split) until ~2 blocks per CU
-        const long nch = pl.K / (bkc * ntap), blocks = (long)pl.mtiles * pl.ntiles * pl.nphase;
-        long splits = 1;
-        while (blocks * splits < target && splits * 4 <= nch) splits *= 2;
-        const long cps = (nch + splits - 1) / splits;
-        pl.kchunk = (int)(cps * bkc * ntap);
-        pl.splits = (int)((nch + cps - 1) / cps);
-        if (hx3 || hx3p || hx3q) pl.x6 = 3;
-        // fp16x3 plans with more patches than resident blocks (2 per CU): each block runs
-        // several patches back to back, the next patch's halo and weights fetched under the
-        // current patch's MFMAs, so a block waits for HBM once instead of once per patch.
-        // ~512 blocks (one per slot) for the stride-2 phases and for 3x3 layers of <= 4
-        // channel chunks per patch (VGG19 block1_conv2 fwd 0.959 -> 0.832 ms, bwd_data 1.000
-        // -> 0.830, G up7 fwd 0.351 -> 0.304, down2 bwd_data 0.220 -> 0.191 at bs32); deeper
-        // 3x3 layers amortise their prologue over >= 72 K-tiles and measured 1-2 % slower at
-        // 512, so ~2048 there (profiles/r5/ab_x3h_persistent.txt)
-        // (DG_X3H_PTILES: patches per block, DG_X3H_PDIV: the block target, for same-box A/B)
-        pl.ptiles = 1;
-        if ((hx3 || hx3p || hx3q) && pl.splits == 1) {
-            const long tot = (long)pl.mtiles * pl.ntiles * pl.nphase;
-            long pdiv = hx3p || nch <= 4 ? 512 : 2048;
-            if (pl.hph == 16) pdiv /= 2;   // (one block per CU)
-            if (const char *e = getenv("DG_X3H_PDIV")) pdiv = std::max(1L, atol(e));
-            long pt = tot / pdiv;
-            if (const char *e = getenv("DG_X3H_PTILES")) pt = atol(e);
-            pl.ptiles = (int)std::max(1L, std::min(pt, 64L));
-        }
-    }
-    if (x3_gen && pl.x6 == 1 && 4.0 * ra * ca < 2.0e9 && 4.0 * rb * cb < 2.0e9) {
-        pl.halo = 0; pl.htx = pl.hty = 0;
-        // short-K forward / input-gradient GEMMs (K = 16 taps x 64..128 channels: G / D down2-3
-        // forwards, the up6 / up7 input gradients): the 64 x 128 tile at K 1024 and 128 x 128 at
-        // K 2048 -- the MFMA-time model's 128 x 256 pick loses there to its prologue / epilogue
-        // share (bs32 sweep: up7 bwd_data 0.406 -> 0.323 ms, D down2 fwd 0.238 -> 0.210, G down3
-        // fwd 0.182 -> 0.167, up6 bwd_data 0.282 -> 0.263; profiles/r5/x3cfg_sweep.txt;
-        // DG_PLAN_DISABLE=x3shortk: the model's pick)
-        const int rule = mode == MODE_WGRAD || pl.N <= 64 || plan_off("x3shortk") ? -1
-                         : (pl.K <= 1024 ? 2 : (pl.K <= 2048 ? 0 : -1));
-        choose_tiles(pl, kX3Cfgs, kNumX3Cfgs, 2516.6e12 / 3.0, "DG_FORCE_X3CFG", rule);
-        pl.x6 = 3;
-    }
-    pl.vec = pl.x6 ? 1 : cfg_vec(g, mode, kCfgs[pl.cfg].bk);
-    pl.slab_bytes = pl.splits > 1 ? (size_t)pl.nphase * pl.splits * pl.M * pl.N * sizeof(float) : 0;
-    pl.ws_bytes = pl.slab_bytes;
-    if (pl.x6) {
-        // workspace: [split-K slabs][A planes][B planes] (6 B per element bf16x6, 2 B fp16, 4 B fp16x3)
-        // (+ fp16x3: 8 floats for max |dy| when no scale source is set)
-        const size_t eb = pl.x6 == 2 ? 2 : (pl.x6 == 3 ? 4 : 6);
-        pl.x6_a_off = (pl.ws_bytes + 255) & ~(size_t)255;
-        pl.x6_b_off = (pl.x6_a_off + eb * ra * ca + 255) & ~(size_t)255;
-        pl.ws_bytes = pl.x6_b_off + eb * rb * cb;
-        if (pl.x6 == 3) {   // (max |dy| and max |x| when no scale source is set: any mode may read dy / x)
-            pl.x3_max_off = (pl.ws_bytes + 255) & ~(size_t)255;
-            pl.ws_bytes = pl.x3_max_off + 2 * X3_SLOT * sizeof(float);
-        }
-    }
-    pl.gemm_bytes = pl.ws_bytes;
-    if (getenv("DG_PLAN_DEBUG"))
-        fprintf(stderr, "[dg plan] mode %d M=%d N=%d K=%d -> %s cfg %d splits %d ph %d ptiles %d\n", mode, pl.M, pl.N, pl.K,
-                pl.halo == 2 ? (pl.x6 == 3 ? "x3h2" : "x6h2") : pl.halo == 4 ? "x6h4" : pl.halo ? (pl.x6 == 2 ? "f16h" : (pl.x6 == 3 ? "x3h" : "x6h")) : (pl.x6 == 2 ? "f16" : (pl.x6 == 3 ? "x3" : (pl.x6 ? "x6" : "fp32"))),
-                pl.cfg, pl.splits, pl.halo ? std::max(8, pl.hph) : 0, pl.ptiles);
-    return pl;
-}
-
-static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-// bytes of the fp16x3 weight planes of a forward plan (x6 3), 256-aligned
-static size_t x3_w_bytes(const OpPlan &pl) { return al256((size_t)4 * pl.x6_rb * pl.x6_cb); }
-
-static ConvGeom geom_1x1(long pixels, int ci, int co) {
-    ConvGeom q{};
-    q.N = 1; q.H = 1; q.W = (int)pixels; q.Ci = ci; q.Ho = 1; q.Wo = (int)pixels; q.Co = co;
-    q.kh = q.kw = q.sh = q.sw = 1; q.pt = q.pl = 0; q.Th = q.Tw = 1;
-    return q;
-}
-
-// (a recast GEMM's operands are gathered / transposed fp32 scratch, not a layer's tensors:
-// DG_MATH_F16X3 descriptors run them bf16x6)
-static int recast_math(const dg_conv_desc_s *d) { return d->math == DG_MATH_F16X3 ? DG_MATH_BF16X6 : d->math; }
-
-// decide whether a narrow op runs as a recast 1x1 MFMA GEMM (+ gather), and size its workspace
-static void plan_recast(dg_conv_desc_s *d, int op) {
-    Recast &rc = d->rc[op];
-    rc = Recast{};
-    if (!d->plan[op].narrow) return;
-    const ConvGeom &g = d->g;
-    const int mode = engine_mode(d, op);
-    const int ntap = g.kh * g.kw;
-    if (mode == MODE_FWD) {
-        if (g.Co != 1 || g.Ci % 32 || ntap % 4 || ntap < 8) return;
-        long P = (long)g.N * g.H * g.W;
-        rc.nv = ntap; rc.nvp = ntap; rc.mode1 = MODE_FWD;
-        rc.g1 = geom_1x1(P, g.Ci, ntap);
-        rc.p1 = make_plan(rc.g1, MODE_FWD, recast_math(d));
-        rc.wt_off = 0;
-        rc.v_off = al256((size_t)g.Ci * ntap * 4);
-        rc.slab_off = al256(rc.v_off + (size_t)P * ntap * 4);
-    } else if (mode == MODE_DGRAD) {
-        const int nv = ntap * g.Ci;
-        if (tlast_ok(g) && !plan_off("tlast")) {
-            d->plan[op].tlast = 1;
-            if (getenv("DG_PLAN_DEBUG")) fprintf(stderr, "[dg plan] mode %d -> tlast\n", mode);
-            return;
-        }
-        if (direct_dgrad_ok(g) && !plan_off("direct")) {
-            d->plan[op].direct = 1;
-            return;
-        }
-        if (g.Co % 32 || nv < 8) return;
-        const int nvp = (nv + 15) & ~15;  // zero-padded columns (e.g. VGG block1_conv1: 3x3x3 = 27 -> 32)
-        long P = (long)g.N * g.Ho * g.Wo;
-        rc.nv = nv; rc.nvp = nvp; rc.mode1 = MODE_FWD;
-        rc.g1 = geom_1x1(P, g.Co, nvp);
-        rc.p1 = make_plan(rc.g1, MODE_FWD, recast_math(d));
-        rc.wt_off = 0;
-        rc.v_off = al256((size_t)g.Co * nvp * 4);
-        rc.slab_off = al256(rc.v_off + (size_t)P * nvp * 4);
-    } else {
-        if (g.Co != 1 || g.Ci % 4 || g.Ci < 8 || ntap % 4) return;
-        long P = (long)g.N * g.H * g.W;
-        rc.nv = ntap; rc.nvp = ntap; rc.mode1 = MODE_WGRAD;
-        rc.g1 = geom_1x1(P, ntap, g.Ci);
-        rc.p1 = make_plan(rc.g1, MODE_WGRAD, recast_math(d));
-        rc.wt_off = 0;
-        rc.v_off = 0;
-        rc.slab_off = al256((size_t)P * ntap * 4);
-    }
-    if (rc.p1.narrow) return;
-    rc.bytes = rc.slab_off + rc.p1.gemm_bytes;
-    rc.on = 1;
-}
-
-static size_t colsum_ws(long M, int C);
-
-// (re)plan the three ops of a descriptor for its math mode
-static void plan_all(dg_conv_desc_s *d) {
-    for (int op = 0; op < 3; ++op) {
-        // (DG_MATH_F16X3: fp16x3 wherever make_plan finds the op eligible, bf16x6 elsewhere)
-        // A filter gradient reads the layer's input and output gradient, whose fp16x3 planes exist
-        // only where the forward / input gradient of the layer runs fp16x3 (the producers write
-        // them for those ops); otherwise its split path also zeroes a max slot and measures the
-        // operand (memset + absmax launches and a read) before splitting it -- G down7 / up2
-        // filter gradients: 37 us of passes around a 27-42 us GEMM (round 6, profiles/r6/calls.txt)
-        double extra = 0.0;
-        if (op == DG_OP_BWD_FILTER && d->math == DG_MATH_F16X3) {
-            const double xin = (double)d->N * d->H * d->W * d->Cin, gout = (double)d->N * d->Ho * d->Wo * d->Cout;
-            if (d->plan[DG_OP_FWD].x6 != 3) extra += 8e-6 + xin * 4.0 / 4.0e12;
-            if (d->plan[DG_OP_BWD_DATA].x6 != 3) extra += 8e-6 + gout * 4.0 / 4.0e12;
-        }
-        d->plan[op] = make_plan(d->g, engine_mode(d, op), d->math, plan_off("wgrad_extra") ? 0.0 : extra);
-        plan_recast(d, op);
-        if (d->rc[op].on) d->plan[op].ws_bytes = d->rc[op].bytes;
-        if (op == DG_OP_BWD_FILTER) {
-            // room for the bias column sum partials after the split-K slabs
-            size_t extra = colsum_ws(1, d->Cout);
-            size_t base = d->rc[op].on ? d->rc[op].bytes : d->plan[op].gemm_bytes;
-            d->plan[op].colsum_off = (base + 255) & ~(size_t)255;
-            d->plan[op].ws_bytes = d->plan[op].colsum_off + extra;
-        }
-    }
-}
-
-static int default_math() {
-    const char *m = getenv("DG_CONV_MATH");
-    if (m && (!strcmp(m, "fp32") || !strcmp(m, "0"))) return DG_MATH_FP32;
-    if (m && (!strcmp(m, "fp16") || !strcmp(m, "2"))) return DG_MATH_FP16;
-    if (m && (!strcmp(m, "f16x3") || !strcmp(m, "3"))) return DG_MATH_F16X3;
-    (void)m;
-    return DG_MATH_BF16X6;
-}
-
-
 template <int MODE>
-static void launch_gemm(int cfg, int vec, dim3 grid, const GemmArgs &a, hipStream_t s) {
-#define DG_L(C, BM_, BN_, WM_, WN_, BK_, MW_)                                                           \
+static int launch_gemm(int cfg, int vec, dim3 grid, const GemmArgs &a, hipStream_t s) {
+#define DG_L(C, BM_, BN_, WM_, WN_, BK_, MW_, NB_, BPC_, EFF_)                                          \
     case C:                                                                                             \
         if (vec) hipLaunchKernelGGL((k_conv_gemm<MODE, BM_, BN_, WM_, WN_, true, BK_, MW_>), grid, dim3(256), 0, s, a); \
         else hipLaunchKernelGGL((k_conv_gemm<MODE, BM_, BN_, WM_, WN_, false, BK_, MW_>), grid, dim3(256), 0, s, a); \
-        break;
+        return DG_OK;
     switch (cfg) {
-        DG_L(0, 128, 128, 2, 2, 32, 2)
-        DG_L(1, 128, 64, 2, 2, 32, 2)
-        DG_L(2, 64, 128, 2, 2, 32, 2)
-        DG_L(3, 64, 64, 2, 2, 32, 2)
-        DG_L(4, 32, 128, 1, 4, 32, 2)
-        DG_L(5, 128, 128, 2, 2, 16, 3)
-        DG_L(6, 128, 64, 2, 2, 16, 3)
-        DG_L(7, 128, 32, 4, 1, 32, 2)
-        DG_L(8, 256, 32, 4, 1, 32, 2)
+        DG_TILES_FP32(DG_L)
+    default:
+        set_error("fp32 conv GEMM: no tile config %d", cfg);
+        return DG_ERR_ARG;
     }
 #undef DG_L
 }
@@ -1821,13 +1212,13 @@ static GemmArgs make_args(const ConvGeom &g, const OpPlan &pl, const float *A, i
     a.mtiles = pl.mtiles; a.ntiles = pl.ntiles; a.nphase = pl.nphase;
     a.slab = (float *)slab;
     a.xcd_plain = plan_off("xcd_phase");
-    a.ptiles = pl.halo ? std::max(1, pl.ptiles) : 1;
+    a.ptiles = is_halo(pl.kern) ? std::max(1, pl.ptiles) : 1;
     // n-grouped XCD raster (xcd_group_tile) for the stride-1 4x4 halo plans (the PatchGAN's conv:
     // 8 n-tiles of 64 columns over 256 patches at bs16 x 2): with every XCD running all 8 n-tiles
     // its L2 streams the whole 8.4 MB fp16x3 filter per round of patches -- the forward read 562 MB
     // for 105 MB of operands (profiles/r5/r5_final_pmc_layers.md); in groups of NG the XCD keeps
     // ntiles / NG column blocks.  DG_XCD_NG: the group count (0: off), for same-box A/B
-    if (pl.halo == 4 && pl.ptiles <= 1 && pl.splits == 1 && pl.nphase == 1) {
+    if (pl.kern == HALO_4x4 && pl.ptiles <= 1 && pl.splits == 1 && pl.nphase == 1) {
         int ng = 4;
         if (const char *e = getenv("DG_XCD_NG")) ng = atoi(e);
         const long tot = (long)pl.mtiles * pl.ntiles;
@@ -1838,16 +1229,7 @@ static GemmArgs make_args(const ConvGeom &g, const OpPlan &pl, const float *A, i
     return a;
 }
 
-// caller-held bf16x6 planes of the two engine operands (dg_conv_planes_t mapped
-// onto A / B of one op): NULL = split into the workspace; ready = already split
-struct PlaneRefs {
-    void *a, *b;
-    int a_ready, b_ready;
-    int b_x6;   // (fp16x3 op, B = w) the weight buffer also holds bf16x6 planes behind the fp16x3 part
-};
-
-static int run_gemm(int mode, const OpPlan &pl, const GemmArgs &a, hipStream_t s, const PlaneRefs *pr = nullptr);
-static bool tensor_x3(const dg_conv_desc_s *d, int t);
+static int run_gemm(int mode, const OpPlan &pl, const GemmArgs &a, hipStream_t s, const PlaneRefs *pr);
 static int finish_splitk(int mode, const OpPlan &pl, const GemmArgs &a, hipStream_t s);
 
 // narrow op through its recast (1x1 MFMA GEMM + gather)
@@ -1857,30 +1239,26 @@ static int run_recast(const dg_conv_desc_s *d, int op, const GemmArgs &a0, char 
     float *wt = (float *)(ws + rc.wt_off);
     float *V = (float *)(ws + rc.v_off);
     void *slab = ws + rc.slab_off;
-    if (rc.mode1 == MODE_FWD && engine_mode(d, op) == MODE_FWD) {
-        // Co == 1: V = x . wt, wt[ci][(i,j)] = w[(i,j)][ci]
-        hipLaunchKernelGGL(k_transpose, dim3(std::min<unsigned>(dg_cdiv((long)rc.nv * g.Ci, 256), 1024)), dim3(256), 0, s,
-                           a0.B, rc.nv, g.Ci, wt, rc.nv);
-        DG_LAUNCHED("recast_transpose");
-        GemmArgs a = make_args(rc.g1, rc.p1, a0.A, a0.lda, wt, rc.nv, V, rc.nv, nullptr, 0.f, DG_ACT_NONE, 0.f, slab);
-        int r = run_gemm(MODE_FWD, rc.p1, a, s);
-        if (r != DG_OK) return r;
-        hipLaunchKernelGGL(k_recast_fwd_gather, dim3(dg_cdiv((long)g.N * g.Ho * g.Wo, 256)), dim3(256), 0, s, a0, V, rc.nv);
-        DG_LAUNCHED("recast_fwd_gather");
-        return DG_OK;
-    }
     if (rc.mode1 == MODE_FWD) {
+        // FWD, Co == 1: V = x . wt, wt[ci][(i,j)] = w[(i,j)][ci]; y = gather of V (nvp == nv)
         // DGRAD, Ci <= 8: V = dy . wt, wt[co][(i,j,ci)] = w[(i,j,ci)][co]; dx = col2im(V)
-        hipLaunchKernelGGL(k_transpose, dim3(std::min<unsigned>(dg_cdiv((long)rc.nvp * g.Co, 256), 1024)), dim3(256), 0, s,
-                           a0.B, rc.nv, g.Co, wt, rc.nvp);
+        const bool fwd = engine_mode(d, op) == MODE_FWD;
+        const int kc = fwd ? g.Ci : g.Co;   // reduction channels: rows of wt
+        hipLaunchKernelGGL(k_transpose, dim3(std::min<unsigned>(dg_cdiv((long)rc.nvp * kc, 256), 1024)), dim3(256), 0, s,
+                           a0.B, rc.nv, kc, wt, rc.nvp);
         DG_LAUNCHED("recast_transpose");
         GemmArgs a = make_args(rc.g1, rc.p1, a0.A, a0.lda, wt, rc.nvp, V, rc.nvp, nullptr, 0.f, DG_ACT_NONE, 0.f, slab);
-        int r = run_gemm(MODE_FWD, rc.p1, a, s);
+        int r = run_gemm(MODE_FWD, rc.p1, a, s, nullptr);
         if (r != DG_OK) return r;
-        long total = (long)g.N * g.H * g.W * g.Ci;
-        hipLaunchKernelGGL(k_recast_col2im, dim3((unsigned)std::min<long>(dg_cdiv(total, 256), 8192)), dim3(256), 0, s,
-                           a0, V, rc.nvp);
-        DG_LAUNCHED("recast_col2im");
+        if (fwd) {
+            hipLaunchKernelGGL(k_recast_fwd_gather, dim3(dg_cdiv((long)g.N * g.Ho * g.Wo, 256)), dim3(256), 0, s, a0, V, rc.nv);
+            DG_LAUNCHED("recast_fwd_gather");
+        } else {
+            long total = (long)g.N * g.H * g.W * g.Ci;
+            hipLaunchKernelGGL(k_recast_col2im, dim3((unsigned)std::min<long>(dg_cdiv(total, 256), 8192)), dim3(256), 0, s,
+                               a0, V, rc.nvp);
+            DG_LAUNCHED("recast_col2im");
+        }
         return DG_OK;
     }
     // WGRAD, Co == 1: G gathered from dy, dw[(i,j)][ci] = G^T . x (a WGRAD GEMM of 1x1 geometry)
@@ -1889,7 +1267,7 @@ static int run_recast(const dg_conv_desc_s *d, int op, const GemmArgs &a0, char 
                        a0, a0.B, a0.ldb, V);
     DG_LAUNCHED("recast_wgrad_gather");
     GemmArgs a = make_args(rc.g1, rc.p1, V, rc.nv, a0.A, a0.lda, a0.C, g.Ci, nullptr, a0.beta, DG_ACT_NONE, 0.f, slab);
-    return run_gemm(MODE_WGRAD, rc.p1, a, s);
+    return run_gemm(MODE_WGRAD, rc.p1, a, s, nullptr);
 }
 
 // outputs of the max pool fused into a forward epilogue (dg_conv_fwd_pool)
@@ -1901,38 +1279,36 @@ struct PoolOut {
     int planes_fmt;   // DG_PLANES_*: the consuming conv's x plane format
 };
 
-// the forward plan of d can run MaxPool2D(2) in its epilogue: the halo-tiled
-// bf16x6 kernel with one split over whole 8 x 16 patches, and an activation
-// whose derivative is a function of the output's sign
-static bool pool_fusable(const dg_conv_desc_s *d, int act) {
-    const OpPlan &pl = d->plan[DG_OP_FWD];
-    return !d->transpose && (pl.x6 == 1 || pl.x6 == 3) && pl.halo == 1 && pl.cfg != 32 && pl.splits == 1 &&
-           !d->rc[DG_OP_FWD].on &&
-           d->g.Ho % (pl.hph == 16 ? 16 : 8) == 0 &&
-           d->g.Wo % 16 == 0 && d->g.Co % 16 == 0 &&
-           (act == DG_ACT_NONE || act == DG_ACT_RELU || act == DG_ACT_LRELU);
-}
+// one call of the engine: the conv-view operands of the op and what its epilogue does
+struct EngineCall {
+    const float *A = nullptr, *B = nullptr;    // operands and strides (op_tensors)
+    float *C = nullptr; int lda = 0, ldb = 0, ldc = 0;
+    const float *bias = nullptr; float beta = 0.f, alpha = 0.f; int act = DG_ACT_NONE;   // epilogue
+    void *ws = nullptr; size_t ws_bytes = 0;
+    // gradient mask of the output (GemmArgs.mz; mact may carry DG_MASK_SUM), or mzp: from the
+    // planes of the activation output
+    const float *mz = nullptr; int ldmz = 0, mact = DG_ACT_NONE; float malpha = 0.f;
+    const unsigned short *mzp = nullptr;
+    PlaneRefs refs{}; const PlaneRefs *pr = nullptr;   // caller-held operand planes (plane_refs: &refs, or none)
+    unsigned short *yp = nullptr; int yp_fmt = DG_PLANES_BF16X6;   // planes of the output beside it
+    const PoolOut *po = nullptr;               // fused max pool
+};
 
-static int run_engine(const dg_conv_desc_s *d, int op, const float *A, int lda, const float *B, int ldb,
-                      float *C, int ldc, const float *bias, float beta, int act, float alpha,
-                      void *ws, size_t ws_bytes, hipStream_t s, const float *mz = nullptr, int ldmz = 0,
-                      int mact = DG_ACT_NONE, float malpha = 0.f, const PlaneRefs *pr = nullptr,
-                      unsigned short *yp = nullptr, const PoolOut *po = nullptr,
-                      const unsigned short *mzp = nullptr, int yp_fmt = DG_PLANES_BF16X6) {
+static int run_engine(const dg_conv_desc_s *d, int op, hipStream_t s, const EngineCall &c) {
     const int mode = engine_mode(d, op);
     const OpPlan &pl = d->plan[op];
     const size_t need = d->rc[op].on ? d->rc[op].bytes : pl.gemm_bytes;
-    DG_ARG(ws_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, ws_bytes);
-    DG_ARG(need == 0 || ws != nullptr, "workspace pointer is NULL");
-    GemmArgs a = make_args(d->g, pl, A, lda, B, ldb, C, ldc, bias, beta, act, alpha, ws);
+    DG_ARG(c.ws_bytes >= need, "workspace too small: need %zu bytes, got %zu", need, c.ws_bytes);
+    DG_ARG(need == 0 || c.ws != nullptr, "workspace pointer is NULL");
+    GemmArgs a = make_args(d->g, pl, c.A, c.lda, c.B, c.ldb, c.C, c.ldc, c.bias, c.beta, c.act, c.alpha, c.ws);
     // (mact | DG_MASK_SUM: the mask also multiplies beta*C -- the conv_epilogue16 / split-K reduce
     // epilogues of the x6 / fp16x3 / fp16 plans implement it)
-    a.mask_acc = (mact & DG_MASK_SUM) ? 1 : 0;
-    mact &= ~DG_MASK_SUM;
-    DG_ARG(!a.mask_acc || (pl.x6 && !d->rc[op].on && (mz || mzp)),
+    a.mask_acc = (c.mact & DG_MASK_SUM) ? 1 : 0;
+    const int mact = c.mact & ~DG_MASK_SUM;
+    DG_ARG(!a.mask_acc || (reads_planes(pl.arith) && !d->rc[op].on && (c.mz || c.mzp)),
            "mask of the accumulated sum: only on the split-precision plans, with a mask");
-    a.mz = mz; a.ldmz = ldmz; a.mact = mact; a.malpha = malpha;
-    if (pl.x6 == 3) {
+    a.mz = c.mz; a.ldmz = c.ldmz; a.mact = mact; a.malpha = c.malpha;
+    if (pl.arith == F16X3) {
         // fp16x3 operand roles (op_tensors): A is x or dy, B is w, or, in a filter gradient,
         // dy or x; dy is scaled from its bound (dg_conv_set_grad_scale's dy source, else
         // measured by run_gemm), x from its source (dg_conv_set_act_scale; else measured by
@@ -1950,27 +1326,27 @@ static int run_engine(const dg_conv_desc_s *d, int op, const float *A, int lda, 
         // the activation scale context: the output planes' source and max |y| (any arithmetic:
         // a forward writes the planes of its consumer)
         a.ys_m = d->as_y_m; a.ys_g = d->as_y_g; a.ys_c = d->as_y_c; a.ymax = d->as_y_max;
-        DG_ARG(!a.ymax || !(pl.narrow || pl.co1 || d->rc[op].on),
+        DG_ARG(!a.ymax || !(is_narrow(pl) || pl.kern == CO1 || d->rc[op].on),
                "max |y| is measured by the GEMM epilogues, the split-K reduce and the small-Cin kernels only (this "
                "forward runs a narrow / Co-1 / recast kernel)");
     }
     if (op == DG_OP_BWD_DATA) {
         // the gradient scale context (dg_conv_set_grad_scale): dx planes' scale source, max |dx|
         a.ys_m = d->gs_dx_m; a.ys_g = d->gs_dx_g; a.ymax = d->gs_dx_max;
-        DG_ARG(!a.ymax || pl.x6 || pl.splits > 1,
+        DG_ARG(!a.ymax || reads_planes(pl.arith) || pl.splits > 1,
                "max |dx| is measured by the 16x16-tile epilogues and the split-K reduce only (plan of this input "
                "gradient: neither)");
-        DG_ARG(yp_fmt != DG_PLANES_F16X3 || a.ys_m,
+        DG_ARG(c.yp_fmt != DG_PLANES_F16X3 || a.ys_m,
                "fp16x3 gradient planes need a scale source (dg_conv_set_grad_scale)");
     }
-    if (po) {
-        DG_ARG(op == DG_OP_FWD && pool_fusable(d, act), "this forward plan cannot fuse the max pool");
+    if (const PoolOut *po = c.po) {
+        DG_ARG(op == DG_OP_FWD && pool_fusable(d, c.act), "this forward plan cannot fuse the max pool");
         DG_ARG(po->idx && (((uintptr_t)po->idx) & 3) == 0, "pool index buffer NULL or not 4-byte aligned");
         DG_ARG(po->y || po->planes, "fused pool writes neither values nor planes");
         DG_ARG(!po->y || (po->ldy % 4 == 0 && po->ldy >= d->g.Co && (((uintptr_t)po->y) & 15) == 0),
                "pooled output needs ldy %% 4 == 0 and 16-byte alignment");
         DG_ARG(!po->planes || (((uintptr_t)po->planes) & 15) == 0, "plane buffers must be 16-byte aligned");
-        DG_ARG(beta == 0.f, "the fused pool overwrites its output (beta must be 0)");
+        DG_ARG(c.beta == 0.f, "the fused pool overwrites its output (beta must be 0)");
         a.pidx = po->idx; a.pool_y = po->y; a.ldpy = po->ldy;
         a.yp = po->planes; a.ypC = d->g.Co;
         if (po->planes && po->planes_fmt == DG_PLANES_F16X3) {
@@ -1978,93 +1354,93 @@ static int run_engine(const dg_conv_desc_s *d, int op, const float *A, int lda, 
             a.ypC = -d->g.Co;
         }
     }
-    if (mzp) {
+    if (c.mzp) {
         // mask from the hi plane's sign: the small-Cin kernels read fp32 masks only
-        DG_ARG(!mz && !pl.small, "plane mask: not with an fp32 mask, nor on the small-Cin kernels");
+        DG_ARG(!c.mz && pl.kern != SMALL, "plane mask: not with an fp32 mask, nor on the small-Cin kernels");
         DG_ARG(mact == DG_ACT_NONE || mact == DG_ACT_RELU || mact == DG_ACT_LRELU,
                "plane mask needs a sign-determined activation (got %d)", mact);
-        a.mzp = mzp; a.mzpC = mode == MODE_FWD ? d->g.Co : d->g.Ci;
+        a.mzp = c.mzp; a.mzpC = mode == MODE_FWD ? d->g.Co : d->g.Ci;
         // (the layer input's planes: fp16x3 when this descriptor's ops read them so)
         if (tensor_x3(d, DG_TENSOR_X)) a.mzpC = -a.mzpC;
     }
-    if (!C && !po) {
+    if (!c.C && !c.po) {
         // planes-only output: the GEMM epilogues skip the fp32 store
-        DG_ARG(yp && beta == 0.f && mode != MODE_WGRAD && !pl.narrow && (!pl.small || mode == MODE_FWD) &&
-                   !d->rc[op].on,
+        DG_ARG(c.yp && c.beta == 0.f && mode != MODE_WGRAD && !is_narrow(pl) &&
+                   (pl.kern != SMALL || mode == MODE_FWD) && !d->rc[op].on,
                "output NULL: only a GEMM-path op writing its output planes (beta 0) may omit it");
     }
     if (pl.M == 0 || pl.N == 0) return DG_OK;
-    if (yp) {
+    if (c.yp) {
         // planes of the output beside it: the GEMM epilogues (fp32, bf16x6,
         // split-K reduce) write them; the narrow / recast paths (output
         // channels < 16, never plane-eligible) are refused
         const int oc = mode == MODE_WGRAD ? 0 : (mode == MODE_FWD ? d->g.Co : d->g.Ci);
-        DG_ARG(oc % 16 == 0 && !pl.narrow && !d->rc[op].on, "output planes need a GEMM path and channels %% 16 == 0");
-        DG_ARG((((uintptr_t)yp) & 15) == 0, "plane buffers must be 16-byte aligned");
-        a.yp = yp; a.ypC = oc;
-        if (yp_fmt == DG_PLANES_F16X3) {
+        DG_ARG(oc % 16 == 0 && !is_narrow(pl) && !d->rc[op].on,
+               "output planes need a GEMM path and channels %% 16 == 0");
+        DG_ARG((((uintptr_t)c.yp) & 15) == 0, "plane buffers must be 16-byte aligned");
+        a.yp = c.yp; a.ypC = oc;
+        if (c.yp_fmt == DG_PLANES_F16X3) {
             DG_ARG(oc % 32 == 0, "fp16x3 output planes need channels %% 32 == 0");
             a.ypC = -oc;
         }
     }
     if (d->rc[op].on) {
-        DG_ARG(lda % 4 == 0 && ((uintptr_t)A & 15) == 0, "recast path needs lda%%4==0 and 16B-aligned A");
-        return run_recast(d, op, a, (char *)ws, s);
+        DG_ARG(c.lda % 4 == 0 && ((uintptr_t)c.A & 15) == 0, "recast path needs lda%%4==0 and 16B-aligned A");
+        return run_recast(d, op, a, (char *)c.ws, s);
     }
-    if (pl.co1) {
-        const ConvGeom &g = d->g;
+    const ConvGeom &g = d->g;
+    switch (pl.kern) {
+    case CO1:
         if (mode == MODE_WGRAD) {
-            DG_ARG(lda % 4 == 0 && ((uintptr_t)A & 15) == 0, "Co == 1 filter gradient needs ldx %% 4 == 0 and 16B-aligned x");
+            DG_ARG(c.lda % 4 == 0 && ((uintptr_t)c.A & 15) == 0, "Co == 1 filter gradient needs ldx %% 4 == 0 and 16B-aligned x");
         } else {
-            DG_ARG(ldb <= 1 && ((uintptr_t)B & 15) == 0, "Co == 1 kernels need a dense 16B-aligned filter");
+            DG_ARG(c.ldb <= 1 && ((uintptr_t)c.B & 15) == 0, "Co == 1 kernels need a dense 16B-aligned filter");
             if (mode == MODE_FWD)
-                DG_ARG(lda % 4 == 0 && ((uintptr_t)A & 15) == 0, "Co == 1 forward needs ldx %% 4 == 0 and 16B-aligned x");
+                DG_ARG(c.lda % 4 == 0 && ((uintptr_t)c.A & 15) == 0, "Co == 1 forward needs ldx %% 4 == 0 and 16B-aligned x");
             else
                 DG_ARG((long)g.N * g.H * g.W * g.Ci < (1L << 31), "operand larger than 2^31 elements");
         }
         launch_co1(mode, a, s);
         DG_LAUNCHED("co1");
         return DG_OK;
-    }
-    if (pl.ntile) {   // (mode == MODE_WGRAD)
+    case NTILE: {   // (mode == MODE_WGRAD)
         float *part = a.slab;
         DG_ARG(part != nullptr, "workspace pointer is NULL");
-        hipLaunchKernelGGL(k_narrow_wgrad_tile, dim3(pl.splits), dim3(256), narrow_tile_lds(d->g), s, a,
-                           narrow_tile_segments(d->g), part);
+        hipLaunchKernelGGL(k_narrow_wgrad_tile, dim3(pl.splits), dim3(256), narrow_tile_lds(g), s, a,
+                           narrow_tile_segments(g), part);
         DG_LAUNCHED("narrow_wgrad_tile");
-        hipLaunchKernelGGL(k_narrow_wgrad_final, dim3(dg_cdiv(pl.M * 4 * narrow_tile_groups(d->g), 16)), dim3(256), 0,
+        hipLaunchKernelGGL(k_narrow_wgrad_final, dim3(dg_cdiv(pl.M * 4 * narrow_tile_groups(g), 16)), dim3(256), 0,
                            s, a, pl.splits, (const float *)part);
         DG_LAUNCHED("narrow_wgrad_final");
         return DG_OK;
     }
-    if (pl.narrow) {
-        const ConvGeom &gg = d->g;
-        const bool px = mode == MODE_FWD && gg.Ci % 4 == 0 && a.lda % 4 == 0 && (((uintptr_t)a.A) & 15) == 0 &&
-                        (gg.Co == 1 || gg.Co == 3) && (long)gg.kh * gg.kw * gg.Ci * gg.Co <= NFWD_WMAX &&
+    case NARROW: case NARROW_DIRECT: case NARROW_TLAST: {
+        const bool px = mode == MODE_FWD && g.Ci % 4 == 0 && a.lda % 4 == 0 && (((uintptr_t)a.A) & 15) == 0 &&
+                        (g.Co == 1 || g.Co == 3) && (long)g.kh * g.kw * g.Ci * g.Co <= NFWD_WMAX &&
                         pl.M >= NFWD_PX_MIN_M && !plan_off("narrow_px");
         if (px) {
             const unsigned grid = (unsigned)std::min<long>(dg_cdiv(pl.M, 256), 8192);
-            if (gg.Co == 1) hipLaunchKernelGGL(k_narrow_fwd_px<1>, dim3(grid), dim3(256), 0, s, a);
+            if (g.Co == 1) hipLaunchKernelGGL(k_narrow_fwd_px<1>, dim3(grid), dim3(256), 0, s, a);
             else hipLaunchKernelGGL(k_narrow_fwd_px<3>, dim3(grid), dim3(256), 0, s, a);
             DG_LAUNCHED("narrow_fwd_px");
         } else if (mode == MODE_FWD) {
             hipLaunchKernelGGL(k_narrow_fwd, dim3(dg_cdiv(pl.M, 4)), dim3(256), 0, s, a);
             DG_LAUNCHED("narrow_fwd");
-        } else if (mode == MODE_DGRAD && pl.tlast && !a.mz && !a.mzp && a.lda % 4 == 0 &&
+        } else if (mode == MODE_DGRAD && pl.kern == NARROW_TLAST && !a.mz && !a.mzp && a.lda % 4 == 0 &&
                    ((((uintptr_t)a.A) | ((uintptr_t)a.B)) & 15) == 0) {
             launch_tlast_fwd(a, s);
             DG_LAUNCHED("tlast_fwd");
-        } else if (mode == MODE_DGRAD && pl.direct && a.lda % 4 == 0 && ((uintptr_t)a.A & 15) == 0) {
+        } else if (mode == MODE_DGRAD && pl.kern == NARROW_DIRECT && a.lda % 4 == 0 && ((uintptr_t)a.A & 15) == 0) {
             launch_direct_dgrad(a, s);
             DG_LAUNCHED("direct_dgrad");
         } else if (mode == MODE_DGRAD) {
-            size_t wbytes = (size_t)d->g.kh * d->g.kw * d->g.Ci * d->g.Co * sizeof(float);
+            size_t wbytes = (size_t)g.kh * g.kw * g.Ci * g.Co * sizeof(float);
             int in_lds = wbytes <= 64 * 1024;
             hipLaunchKernelGGL(k_narrow_dgrad, dim3(dg_cdiv(pl.M, 256), pl.nphase), dim3(256), in_lds ? wbytes : 0, s, a, in_lds);
             DG_LAUNCHED("narrow_dgrad");
         } else {
             a.splits = pl.splits; a.kchunk = pl.kchunk;
-            hipLaunchKernelGGL(k_narrow_wgrad, dim3(d->g.kh * d->g.kw * ((d->g.Ci + 255) / 256), pl.splits), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_narrow_wgrad, dim3(g.kh * g.kw * ((g.Ci + 255) / 256), pl.splits), dim3(256), 0, s, a);
             DG_LAUNCHED("narrow_wgrad");
             long total = (long)pl.M * pl.N;
             hipLaunchKernelGGL(k_splitk_reduce<MODE_WGRAD>, dim3((unsigned)std::min<long>(dg_cdiv(total, 256), 2048), 1), dim3(256), 0, s, a, 0);
@@ -2072,235 +1448,204 @@ static int run_engine(const dg_conv_desc_s *d, int op, const float *A, int lda, 
         }
         return DG_OK;
     }
-    if (pl.small) {
-        const ConvGeom &g = d->g;
+    case SMALL: {
         const long xin = (long)g.N * g.H * g.W, xout = (long)g.N * g.Ho * g.Wo;
-        DG_ARG((xin - 1) * lda + g.Ci < (1L << 31) && xout * ldb < (1L << 31) && xout * ldc < (1L << 31),
+        DG_ARG((xin - 1) * c.lda + g.Ci < (1L << 31) && xout * c.ldb < (1L << 31) && xout * c.ldc < (1L << 31),
                "operand larger than 2^31 elements");
         launch_small_conv(mode, a, pl.small_rows, s);
         DG_LAUNCHED(mode == MODE_WGRAD ? "small_wgrad" : "small_fwd");
         return finish_splitk(mode, pl, a, s);
     }
-    return run_gemm(mode, pl, a, s, pr);
+    default:
+        return run_gemm(mode, pl, a, s, c.pr);
+    }
+}
+
+// The splitters of run_gemm: the operands that are not ready go into planes at pa / pb (the
+// caller-held buffers, else the workspace).
+// bf16x6: bf16 hi/mid/lo planes
+static int split_x6(const OpPlan &pl, const GemmArgs &a, int ldbw, void *pa, void *pb, bool a_ready, bool b_ready,
+                     hipStream_t s) {
+    if (!a_ready) {
+        launch_split3(a.A, a.lda, pl.x6_ra, pl.x6_ca, (unsigned short *)pa, s);
+        DG_LAUNCHED("split3_a");
+    }
+    if (!b_ready) {
+        launch_split3(a.B, ldbw, pl.x6_rb, pl.x6_cb, (unsigned short *)pb, s);
+        DG_LAUNCHED("split3_b");
+    }
+    return DG_OK;
+}
+
+// fp16: round the operands into one fp16 plane each -- the caller-held
+// copies (dg_conv_planes_t: a layer's x, dy and w are converted once
+// and shared by the ops that read them) or the workspace; both in one launch
+static int split_f16(const OpPlan &pl, const GemmArgs &a, int ldbw, void *pa, void *pb, bool a_ready, bool b_ready,
+                      hipStream_t s) {
+    if (!a_ready && !b_ready) {
+        launch_split_f16_pair(a.A, a.lda, pl.x6_ra, pl.x6_ca, pa, a.B, ldbw, pl.x6_rb, pl.x6_cb, pb, s);
+        DG_LAUNCHED("split_f16");
+    } else if (!a_ready) {
+        launch_split_f16(a.A, a.lda, pl.x6_ra, pl.x6_ca, pa, s);
+        DG_LAUNCHED("split_f16_a");
+    } else if (!b_ready) {
+        launch_split_f16(a.B, ldbw, pl.x6_rb, pl.x6_cb, pb, s);
+        DG_LAUNCHED("split_f16_b");
+    }
+    return DG_OK;
+}
+
+// fp16x3: activations / gradients -> fp16x3 planes in 32-channel groups, weights in
+// 16-column groups (common.h); a caller-held weight buffer also receives the
+// weights' bf16x6 planes behind them when a bf16x6 op of the layer reads them
+// (tensor_plane_bytes).  The gradient operand (a.x3_dyn) is scaled from its bound:
+// a.as_m / as_g, the caller's scale source, else max |dy| measured here
+static int split_x3(int mode, const OpPlan &pl, GemmArgs &a, int ldbw, void *pa, void *pb, bool a_ready, bool b_ready,
+                    const PlaneRefs *pr, hipStream_t s) {
+    DG_ARG(a.x3_sa > 0.f && a.x3_sb > 0.f, "fp16x3 GEMM without its operand roles (run_engine)");
+    char *ws = (char *)a.slab;
+    const bool b_w = mode != MODE_WGRAD;                    // B is the weight tensor
+    // an operand without a scale source is measured before its split: max |value| into the
+    // workspace -- a gradient always (its planes must not be ready), an activation whose
+    // planes live in the workspace (caller-held activation planes without a source keep the
+    // static F16X3_XS, the producers' default); an activation source that is a plain max
+    // slot (g, c unset) is measured into by the op that splits x
+    for (int o = 1; o <= 2; ++o) {
+        const bool is_a = o == 1;
+        if (!is_a && b_w) continue;
+        const float *&m = is_a ? a.as_m : a.bs_m, *&sg = is_a ? a.as_g : a.bs_g, *&sc = is_a ? a.as_c : a.bs_c;
+        const bool ready = is_a ? a_ready : b_ready;
+        const bool held = is_a ? (pr && pr->a) : (pr && pr->b);
+        const bool grad = a.x3_dyn == o;
+        float *meas = nullptr;
+        if (!m) {
+            DG_ARG(!grad || !ready, "fp16x3 dy planes given without their scale source (dg_conv_set_grad_scale)");
+            if (!grad && held) continue;
+            meas = (float *)(ws + pl.x3_max_off + (grad ? 0 : X3_SLOT * sizeof(float)));
+        } else if (!ready && !sg && !sc && !grad) {
+            meas = const_cast<float *>(m);   // an x source that is a plain max slot: measured by this split
+        }
+        if (!meas) continue;
+        if (hipMemsetAsync(meas, 0, X3_SLOT * sizeof(float), s) != hipSuccess) {
+            dg::set_error("hipMemsetAsync failed");
+            return DG_ERR_HIP;
+        }
+        if (is_a) launch_absmax(a.A, pl.x6_ra, pl.x6_ca, a.lda, meas, s);
+        else launch_absmax(a.B, pl.x6_rb, pl.x6_cb, a.ldb, meas, s);
+        DG_LAUNCHED("absmax_operand");
+        m = meas; sg = sc = nullptr;
+    }
+    if (!a_ready) {
+        launch_split_x3(a.A, a.lda, pl.x6_ra, pl.x6_ca, pa, 32, a.x3_sa, s, a.as_m, a.as_g, a.as_c);
+        DG_LAUNCHED("split_x3_a");
+    }
+    if (!b_ready) {
+        if (!b_w) {
+            launch_split_x3(a.B, a.ldb, pl.x6_rb, pl.x6_cb, pb, 32, a.x3_sb, s, a.bs_m, a.bs_g, a.bs_c);
+            DG_LAUNCHED("split_x3_b");
+        } else {
+            launch_split_x3(a.B, ldbw, pl.x6_rb, pl.x6_cb, pb, 16, F16X3_WS, s);
+            DG_LAUNCHED("split_x3_w");
+            if (pr && pr->b && pr->b_x6) {
+                launch_split3(a.B, ldbw, pl.x6_rb, pl.x6_cb, (unsigned short *)((char *)pb + pr->b_x6), s);
+                DG_LAUNCHED("split3_w");
+            }
+        }
+    }
+    return DG_OK;
 }
 
 static int run_gemm(int mode, const OpPlan &pl, const GemmArgs &a_in, hipStream_t s, const PlaneRefs *pr) {
     GemmArgs a = a_in;
-    const float *A = a.A, *B = a.B;
-    const int lda = a.lda, ldb = a.ldb;
     {   // operand extents for the buffer-resource range checks
         const ConvGeom &g = a.g;
         const long xin = (long)g.N * g.H * g.W, xout = (long)g.N * g.Ho * g.Wo;
-        long ab, bb;
-        if (mode == MODE_FWD) {
-            ab = ((xin - 1) * lda + g.Ci) * 4;
-            bb = ((long)(pl.K - 1) * ldb + pl.N) * 4;
-        } else if (mode == MODE_DGRAD) {
-            ab = ((xout - 1) * lda + g.Co) * 4;
-            bb = (long)g.kh * g.kw * g.Ci * g.Co * 4;
-        } else {
-            ab = ((xin - 1) * lda + g.Ci) * 4;
-            bb = ((xout - 1) * ldb + g.Co) * 4;
-        }
+        const long ab = mode == MODE_DGRAD ? ((xout - 1) * a.lda + g.Co) * 4 : ((xin - 1) * a.lda + g.Ci) * 4;
+        const long bb = mode == MODE_FWD ? ((long)(pl.K - 1) * a.ldb + pl.N) * 4
+                        : (mode == MODE_DGRAD ? (long)g.kh * g.kw * g.Ci * g.Co * 4 : ((xout - 1) * a.ldb + g.Co) * 4);
         DG_ARG(ab < (1L << 31) && bb < (1L << 31), "operand larger than 2 GiB (buffer-resource offsets are 32-bit)");
-        a.a_bytes = (unsigned)ab;
-        a.b_bytes = (unsigned)bb;
+        a.a_bytes = (unsigned)ab; a.b_bytes = (unsigned)bb;
     }
-    if (pl.x6 == 3) {
-        // fp16x3: activations / gradients -> fp16x3 planes in 32-channel groups, weights in
-        // 16-column groups (common.h); a caller-held weight buffer also receives the
-        // weights' bf16x6 planes behind them when a bf16x6 op of the layer reads them
-        // (tensor_plane_bytes).  The gradient operand (a.x3_dyn) is scaled from its bound:
-        // a.as_m / as_g, the caller's scale source, else max |dy| measured here
-        char *ws = (char *)a.slab;
-        DG_ARG(ws != nullptr, "workspace pointer is NULL");
-        DG_ARG(a.x3_sa > 0.f && a.x3_sb > 0.f, "fp16x3 GEMM without its operand roles (run_engine)");
-        void *pa = ws + pl.x6_a_off, *pb = ws + pl.x6_b_off;
-        const bool b_w = mode != MODE_WGRAD;                    // B is the weight tensor
-        const int ldbw = (mode == MODE_DGRAD) ? a.g.Co : ldb;   // DGRAD B is the dense weight tensor
-        if (pr && pr->a) pa = pr->a;
-        if (pr && pr->b) pb = pr->b;
-        const bool a_ready = pr && pr->a && pr->a_ready;
-        const bool b_ready = pr && pr->b && pr->b_ready;
-        // an operand without a scale source is measured before its split: max |value| into the
-        // workspace -- a gradient always (its planes must not be ready), an activation whose
-        // planes live in the workspace (caller-held activation planes without a source keep the
-        // static F16X3_XS, the producers' default); an activation source that is a plain max
-        // slot (g, c unset) is measured into by the op that splits x
-        for (int o = 1; o <= 2; ++o) {
-            const bool is_a = o == 1;
-            if (!is_a && b_w) continue;
-            const float *&m = is_a ? a.as_m : a.bs_m;
-            const bool ready = is_a ? a_ready : b_ready;
-            const bool held = is_a ? (pr && pr->a) : (pr && pr->b);
-            const bool grad = a.x3_dyn == o;
-            float *meas = nullptr;
-            if (!m) {
-                DG_ARG(!grad || !ready, "fp16x3 dy planes given without their scale source (dg_conv_set_grad_scale)");
-                if (!grad && held) continue;
-                meas = (float *)(ws + pl.x3_max_off + (grad ? 0 : X3_SLOT * sizeof(float)));
-            } else if (!ready && (is_a ? !a.as_g && !a.as_c : !a.bs_g && !a.bs_c) && !grad) {
-                meas = const_cast<float *>(m);   // an x source that is a plain max slot: measured by this split
-            }
-            if (!meas) continue;
-            if (hipMemsetAsync(meas, 0, X3_SLOT * sizeof(float), s) != hipSuccess) {
-                dg::set_error("hipMemsetAsync failed");
-                return DG_ERR_HIP;
-            }
-            if (is_a) launch_absmax(A, pl.x6_ra, pl.x6_ca, lda, meas, s);
-            else launch_absmax(B, pl.x6_rb, pl.x6_cb, ldb, meas, s);
-            DG_LAUNCHED("absmax_operand");
-            if (is_a) { a.as_m = meas; a.as_g = nullptr; a.as_c = nullptr; }
-            else { a.bs_m = meas; a.bs_g = nullptr; a.bs_c = nullptr; }
-        }
-        if (!a_ready) {
-            launch_split_x3(A, lda, pl.x6_ra, pl.x6_ca, pa, 32, a.x3_sa, s, a.as_m, a.as_g, a.as_c);
-            DG_LAUNCHED("split_x3_a");
-        }
-        if (!b_ready) {
-            if (!b_w) {
-                launch_split_x3(B, ldb, pl.x6_rb, pl.x6_cb, pb, 32, a.x3_sb, s, a.bs_m, a.bs_g, a.bs_c);
-                DG_LAUNCHED("split_x3_b");
-            } else {
-                launch_split_x3(B, ldbw, pl.x6_rb, pl.x6_cb, pb, 16, F16X3_WS, s);
-                DG_LAUNCHED("split_x3_w");
-                if (pr && pr->b && pr->b_x6) {
-                    launch_split3(B, ldbw, pl.x6_rb, pl.x6_cb, (unsigned short *)((char *)pb + x3_w_bytes(pl)), s);
-                    DG_LAUNCHED("split3_w");
-                }
-            }
-        }
-        a.A = (const float *)pa; a.lda = pl.x6_ca; a.a_bytes = (unsigned)(4 * pl.x6_ra * pl.x6_ca);
-        a.B = (const float *)pb; a.ldb = pl.x6_cb; a.b_bytes = (unsigned)(4 * pl.x6_rb * pl.x6_cb);
-        dim3 grid(pl.mtiles * pl.ntiles, pl.nphase * pl.splits);
-        if (pl.halo) {
-            // (persistent blocks: patch row mt0 + j * gm, j < ptiles, of each of the gm * ntiles blocks)
-            grid.x = (unsigned)((pl.mtiles + a.ptiles - 1) / a.ptiles * pl.ntiles);
-            launch_gemm_x6h(mode, pl.cfg, pl.halo == 2 ? 2 : (pl.halo == 4 ? 4 : 3), grid, a, pl.htx, pl.hty, s, 4,
-                            pl.hph == 16 ? 16 : 8);
-            DG_LAUNCHED("conv_gemm_x3h");
-        } else {
-            fastdiv_magic((unsigned)a.g.Wo, a.mg_wo, a.sh_wo);
-            fastdiv_magic((unsigned)a.g.Ho, a.mg_ho, a.sh_ho);
-            launch_gemm_x3(mode, pl.cfg, grid, a, s);
-            DG_LAUNCHED("conv_gemm_x3");
-        }
-        return finish_splitk(mode, pl, a, s);
-    }
-    if (pl.x6 == 2) {
-        // fp16: round the operands into one fp16 plane each -- the caller-held
-        // copies (dg_conv_planes_t: a layer's x, dy and w are converted once
-        // and shared by the ops that read them) or the workspace
-        char *ws = (char *)a.slab;
-        DG_ARG(ws != nullptr, "workspace pointer is NULL");
-        void *pa = ws + pl.x6_a_off, *pb = ws + pl.x6_b_off;
-        const int ldbw = (mode == MODE_DGRAD) ? a.g.Co : ldb;
-        if (pr && pr->a) pa = pr->a;
-        if (pr && pr->b) pb = pr->b;
-        const bool need_a = !(pr && pr->a && pr->a_ready), need_b = !(pr && pr->b && pr->b_ready);
-        if (need_a && need_b) {
-            launch_split_f16_pair(A, lda, pl.x6_ra, pl.x6_ca, pa, B, ldbw, pl.x6_rb, pl.x6_cb, pb, s);
-            DG_LAUNCHED("split_f16");
-        } else if (need_a) {
-            launch_split_f16(A, lda, pl.x6_ra, pl.x6_ca, pa, s);
-            DG_LAUNCHED("split_f16_a");
-        } else if (need_b) {
-            launch_split_f16(B, ldbw, pl.x6_rb, pl.x6_cb, pb, s);
-            DG_LAUNCHED("split_f16_b");
-        }
-        a.A = (const float *)pa; a.lda = pl.x6_ca; a.a_bytes = (unsigned)(2 * pl.x6_ra * pl.x6_ca);
-        a.B = (const float *)pb; a.ldb = pl.x6_cb; a.b_bytes = (unsigned)(2 * pl.x6_rb * pl.x6_cb);
-        fastdiv_magic((unsigned)a.g.Wo, a.mg_wo, a.sh_wo);
-        fastdiv_magic((unsigned)a.g.Ho, a.mg_ho, a.sh_ho);
-        DG_ARG(a.yp == nullptr, "fp16 conv math writes no bf16x6 output planes");
-        dim3 grid(pl.mtiles * pl.ntiles, pl.nphase * pl.splits);
-        if (pl.halo) launch_gemm_x6h(mode, pl.cfg, 3, grid, a, pl.htx, pl.hty, s, 2);
-        else launch_gemm_f16(mode, pl.cfg, grid, a, s);
-        DG_LAUNCHED("conv_gemm_f16");
-        return finish_splitk(mode, pl, a, s);
-    }
-    if (pl.x6) {
-        // split both operands into bf16 hi/mid/lo planes in the workspace, then
-        // point the GEMM at plane 0 of each (dense rows of x6_ca / x6_cb)
-        char *ws = (char *)a.slab;
-        DG_ARG(ws != nullptr, "workspace pointer is NULL");
-        unsigned short *pa = (unsigned short *)(ws + pl.x6_a_off);
-        unsigned short *pb = (unsigned short *)(ws + pl.x6_b_off);
-        const long pas = pl.x6_ra * pl.x6_ca, pbs = pl.x6_rb * pl.x6_cb;
-        const int ldbw = (mode == MODE_DGRAD) ? a.g.Co : ldb;  // DGRAD B is the dense weight tensor
-        if (pr && pr->a) pa = (unsigned short *)pr->a;
-        if (pr && pr->b) pb = (unsigned short *)pr->b;
-        if (!(pr && pr->a && pr->a_ready)) {
-            launch_split3(A, lda, pl.x6_ra, pl.x6_ca, pa, s);
-            DG_LAUNCHED("split3_a");
-        }
-        if (!(pr && pr->b && pr->b_ready)) {
-            launch_split3(B, ldbw, pl.x6_rb, pl.x6_cb, pb, s);
-            DG_LAUNCHED("split3_b");
-        }
-        a.A = (const float *)pa; a.lda = pl.x6_ca; a.a_bytes = (unsigned)(3 * pas * 2);
-        fastdiv_magic((unsigned)a.g.Wo, a.mg_wo, a.sh_wo);
-        fastdiv_magic((unsigned)a.g.Ho, a.mg_ho, a.sh_ho);
-        a.B = (const float *)pb; a.ldb = pl.x6_cb; a.b_bytes = (unsigned)(3 * pbs * 2);
-        dim3 grid(pl.mtiles * pl.ntiles, pl.nphase * pl.splits);
-        if (pl.halo) launch_gemm_x6h(mode, pl.cfg, pl.halo == 2 ? 2 : (pl.halo == 4 ? 4 : 3), grid, a, pl.htx, pl.hty, s);
-        else launch_gemm_x6(mode, pl.cfg, grid, a, s);
-        DG_LAUNCHED("conv_gemm_x6");
-        return finish_splitk(mode, pl, a, s);
-    }
-    if (mode == MODE_FWD || mode == MODE_WGRAD) {
-        DG_ARG(pl.N % 4 == 0 && ldb % 4 == 0, "GEMM N (%d) and ldb (%d) must be multiples of 4", pl.N, ldb);
-    }
-    if (pl.vec) {
-        DG_ARG(lda % 4 == 0 && ((uintptr_t)A & 15) == 0, "vector path needs lda%%4==0 and 16B-aligned A");
-    }
-    DG_ARG(((uintptr_t)B & 15) == 0 || mode == MODE_DGRAD, "B must be 16B aligned");
     dim3 grid(pl.mtiles * pl.ntiles, pl.nphase * pl.splits);
-    switch (mode) {
-    case MODE_FWD: launch_gemm<MODE_FWD>(pl.cfg, pl.vec, grid, a, s); break;
-    case MODE_DGRAD: launch_gemm<MODE_DGRAD>(pl.cfg, pl.vec, grid, a, s); break;
-    default: launch_gemm<MODE_WGRAD>(pl.cfg, pl.vec, grid, a, s); break;
+    int r;
+    if (!reads_planes(pl.arith)) {
+        if (mode == MODE_FWD || mode == MODE_WGRAD)
+            DG_ARG(pl.N % 4 == 0 && a.ldb % 4 == 0, "GEMM N (%d) and ldb (%d) must be multiples of 4", pl.N, a.ldb);
+        if (pl.vec)
+            DG_ARG(a.lda % 4 == 0 && ((uintptr_t)a.A & 15) == 0, "vector path needs lda%%4==0 and 16B-aligned A");
+        DG_ARG(((uintptr_t)a.B & 15) == 0 || mode == MODE_DGRAD, "B must be 16B aligned");
+        switch (mode) {
+        case MODE_FWD: r = launch_gemm<MODE_FWD>(pl.cfg, pl.vec, grid, a, s); break;
+        case MODE_DGRAD: r = launch_gemm<MODE_DGRAD>(pl.cfg, pl.vec, grid, a, s); break;
+        default: r = launch_gemm<MODE_WGRAD>(pl.cfg, pl.vec, grid, a, s); break;
+        }
+        if (r != DG_OK) return r;
+        DG_LAUNCHED("conv_gemm");
+        return finish_splitk(mode, pl, a, s);
     }
-    DG_LAUNCHED("conv_gemm");
+    // split the operands that are not ready into planes -- the caller's buffers or the
+    // workspace -- then point the GEMM at them (dense rows of x6_ca / x6_cb)
+    char *ws = (char *)a.slab;
+    DG_ARG(ws != nullptr, "workspace pointer is NULL");
+    void *pa = pr && pr->a ? pr->a : ws + pl.x6_a_off, *pb = pr && pr->b ? pr->b : ws + pl.x6_b_off;
+    const bool a_ready = pr && pr->a && pr->a_ready, b_ready = pr && pr->b && pr->b_ready;
+    const int ldbw = (mode == MODE_DGRAD) ? a.g.Co : a.ldb;  // DGRAD B is the dense weight tensor
+    r = pl.arith == F16X3 ? split_x3(mode, pl, a, ldbw, pa, pb, a_ready, b_ready, pr, s)
+        : (pl.arith == FP16 ? split_f16(pl, a, ldbw, pa, pb, a_ready, b_ready, s)
+                            : split_x6(pl, a, ldbw, pa, pb, a_ready, b_ready, s));
+    if (r != DG_OK) return r;
+    const long eb = plane_elem_bytes(pl.arith);
+    a.A = (const float *)pa; a.lda = pl.x6_ca; a.a_bytes = (unsigned)(eb * pl.x6_ra * pl.x6_ca);
+    a.B = (const float *)pb; a.ldb = pl.x6_cb; a.b_bytes = (unsigned)(eb * pl.x6_rb * pl.x6_cb);
+    // (read by the implicit-GEMM kernel's WGRAD only; the halo kernel ignores them)
+    fastdiv_magic((unsigned)a.g.Wo, a.mg_wo, a.sh_wo);
+    fastdiv_magic((unsigned)a.g.Ho, a.mg_ho, a.sh_ho);
+    if (pl.arith == FP16) DG_ARG(a.yp == nullptr, "fp16 conv math writes no bf16x6 output planes");
+    const bool halo = is_halo(pl.kern);
+    if (halo) {
+        // (persistent blocks: patch row mt0 + j * gm, j < ptiles, of each of the gm * ntiles blocks)
+        grid.x = (unsigned)((pl.mtiles + a.ptiles - 1) / a.ptiles * pl.ntiles);
+        launch_gemm_x6h(mode, pl.hbn, halo_taps(pl.kern), grid, a, pl.htx, pl.hty, s,
+                        pl.arith == F16X3 ? 4 : (pl.arith == FP16 ? 2 : 3), pl.hph == 16 ? 16 : 8);
+    } else {
+        r = pl.arith == F16X3 ? launch_gemm_x3(mode, pl.cfg, grid, a, s)
+            : (pl.arith == FP16 ? launch_gemm_f16(mode, pl.cfg, grid, a, s) : launch_gemm_x6(mode, pl.cfg, grid, a, s));
+        if (r != DG_OK) return r;
+    }
+    DG_LAUNCHED(pl.arith == F16X3 ? (halo ? "conv_gemm_x3h" : "conv_gemm_x3")
+                                  : (pl.arith == FP16 ? "conv_gemm_f16" : "conv_gemm_x6"));
     return finish_splitk(mode, pl, a, s);
 }
 
 // split-K reduction + epilogue of a GEMM whose kernel wrote partial slabs
 static int finish_splitk(int mode, const OpPlan &pl, const GemmArgs &a, hipStream_t s) {
-    if (pl.splits > 1) {
-        // float4 outputs with tpo lanes per output (tpo = 0 -> scalar path)
-        // (tpo lanes per float4 output until ~256K threads read the slabs, each lane summing >= 4)
-        int tpo = 0;
-        if ((pl.N % 4 == 0) && (a.ldc % 4 == 0) && ((((uintptr_t)a.C) | ((uintptr_t)a.slab)) & 15) == 0) {
-            tpo = 1;
-            const long E = (long)pl.M * pl.N / 4 * pl.nphase;
-            while (tpo < 64 && tpo * 4 <= pl.splits && E * tpo < 262144) tpo <<= 1;
-        }
-        const int v4 = tpo;
-        long total = tpo ? (long)pl.M * pl.N / 4 * tpo : (long)pl.M * pl.N;
-        dim3 rg((unsigned)std::min<long>(dg_cdiv(total, 256), 4096), pl.nphase);
-        static const bool trace = getenv("DG_TRACE_REDUCE") != nullptr;
-        if (trace)
-            fprintf(stderr, "[reduce] mode %d M %ld N %d splits %d nphase %d tpo %d grid %u C %d beta %g bias %d yp %d ymax %d mz %d mzp %d ys_m %d\n",
-                    mode, (long)pl.M, pl.N, pl.splits, pl.nphase, tpo, rg.x, a.C != nullptr, a.beta, a.bias != nullptr,
-                    a.yp != nullptr, a.ymax != nullptr, a.mz != nullptr, a.mzp != nullptr, a.ys_m != nullptr);
-        switch (mode) {
-        case MODE_FWD: hipLaunchKernelGGL(k_splitk_reduce<MODE_FWD>, rg, dim3(256), 0, s, a, v4); break;
-        case MODE_DGRAD: hipLaunchKernelGGL(k_splitk_reduce<MODE_DGRAD>, rg, dim3(256), 0, s, a, v4); break;
-        default: hipLaunchKernelGGL(k_splitk_reduce<MODE_WGRAD>, rg, dim3(256), 0, s, a, v4); break;
-        }
-        DG_LAUNCHED("splitk_reduce");
+    if (pl.splits <= 1) return DG_OK;
+    // float4 outputs with tpo lanes per output (tpo = 0 -> scalar path)
+    // (tpo lanes per float4 output until ~256K threads read the slabs, each lane summing >= 4)
+    int tpo = 0;
+    if ((pl.N % 4 == 0) && (a.ldc % 4 == 0) && ((((uintptr_t)a.C) | ((uintptr_t)a.slab)) & 15) == 0) {
+        tpo = 1;
+        const long E = (long)pl.M * pl.N / 4 * pl.nphase;
+        while (tpo < 64 && tpo * 4 <= pl.splits && E * tpo < 262144) tpo <<= 1;
     }
+    long total = tpo ? (long)pl.M * pl.N / 4 * tpo : (long)pl.M * pl.N;
+    dim3 rg((unsigned)std::min<long>(dg_cdiv(total, 256), 4096), pl.nphase);
+    static const bool trace = getenv("DG_TRACE_REDUCE") != nullptr;
+    if (trace)
+        fprintf(stderr, "[reduce] mode %d M %ld N %d splits %d nphase %d tpo %d grid %u C %d beta %g bias %d yp %d ymax %d mz %d mzp %d ys_m %d\n",
+                mode, (long)pl.M, pl.N, pl.splits, pl.nphase, tpo, rg.x, a.C != nullptr, a.beta, a.bias != nullptr,
+                a.yp != nullptr, a.ymax != nullptr, a.mz != nullptr, a.mzp != nullptr, a.ys_m != nullptr);
+    switch (mode) {
+    case MODE_FWD: hipLaunchKernelGGL(k_splitk_reduce<MODE_FWD>, rg, dim3(256), 0, s, a, tpo); break;
+    case MODE_DGRAD: hipLaunchKernelGGL(k_splitk_reduce<MODE_DGRAD>, rg, dim3(256), 0, s, a, tpo); break;
+    default: hipLaunchKernelGGL(k_splitk_reduce<MODE_WGRAD>, rg, dim3(256), 0, s, a, tpo); break;
+    }
+    DG_LAUNCHED("splitk_reduce");
     return DG_OK;
 }
 
-static size_t colsum_ws(long M, int C) {
-    (void)M;
-    return (size_t)C * 1024 * sizeof(float);
-}
-
 static int run_colsum(const float *dy, int ld, long M, int C, float *out, float beta, float *ws, hipStream_t s) {
-    // row chunks of >= 256 rows (<= 64 loads per lane), at most 1024 (colsum_ws)
+    // row chunks of >= 256 rows (<= 64 loads per lane), at most 1024 (conv_plan.hip colsum_ws)
     int nblk = (int)std::min<long>(1024, std::max<long>(1, dg_cdiv(M, 256)));
     long rpb = (M + nblk - 1) / nblk;
     int cc = 1;
@@ -2312,75 +1657,23 @@ static int run_colsum(const float *dy, int ld, long M, int C, float *out, float 
     return DG_OK;
 }
 
-// layer tensors (DG_TENSOR_*) read as engine operands A and B by op
-static void op_tensors(const dg_conv_desc_s *d, int op, int &ta, int &tb) {
-    if (op == DG_OP_FWD) { ta = DG_TENSOR_X; tb = DG_TENSOR_W; }
-    else if (op == DG_OP_BWD_DATA) { ta = DG_TENSOR_DY; tb = DG_TENSOR_W; }
-    else if (!d->transpose) { ta = DG_TENSOR_X; tb = DG_TENSOR_DY; }
-    else { ta = DG_TENSOR_DY; tb = DG_TENSOR_X; }  // conv view of a transposed layer: A = its output grad
-}
-
-// an op that reads operand planes at all: bf16x6 (x6 1), the fp16 copy (x6 2,
-// DG_MATH_FP16: [rows][C] fp16, the same for every op that reads the tensor) or fp16x3
-// (x6 3); fp32 / narrow / recast plans read fp32
-static bool op_reads_planes(const dg_conv_desc_s *d, int op) {
-    const OpPlan &pl = d->plan[op];
-    if ((pl.x6 != 1 && pl.x6 != 2 && pl.x6 != 3) || pl.narrow || d->rc[op].on || pl.M == 0 || pl.N == 0) return false;
-    return !(pl.x6 == 2 && plan_off("f16planes"));
-}
-// tensor t's planes are fp16x3 when an fp16x3 op reads them; a bf16x6 op of the same
-// layer then splits that tensor itself, except w, whose buffer holds [fp16x3 | bf16x6]
-static bool tensor_reader(const dg_conv_desc_s *d, int t, int x6) {
-    for (int op = 0; op < 3; ++op) {
-        int ta, tb;
-        op_tensors(d, op, ta, tb);
-        if (((ta | tb) & t) && op_reads_planes(d, op) && d->plan[op].x6 == x6) return true;
-    }
-    return false;
-}
-static bool tensor_x3(const dg_conv_desc_s *d, int t) { return tensor_reader(d, t, 3); }
-static size_t x3_wbytes(const dg_conv_desc_s *d) {
-    return al256((size_t)4 * d->g.kh * d->g.kw * d->Cin * d->Cout);
-}
-static size_t tensor_plane_bytes(const dg_conv_desc_s *d, int t) {
-    const size_t nw = (size_t)d->g.kh * d->g.kw * d->Cin * d->Cout;
-    if (t == DG_TENSOR_X) return (size_t)(tensor_x3(d, t) ? 4 : 6) * d->N * d->H * d->W * d->Cin;
-    if (t == DG_TENSOR_DY) return (size_t)(tensor_x3(d, t) ? 4 : 6) * d->N * d->Ho * d->Wo * d->Cout;
-    if (!tensor_x3(d, t)) return 6 * nw;
-    return x3_wbytes(d) + (tensor_reader(d, t, 1) ? 6 * nw : 0);
-}
-
-// tensors op reads as operand planes (op_reads_planes); x and dy only in the format
-// tensor_x3 gives them
-static int op_plane_mask(const dg_conv_desc_s *d, int op) {
-    if (!op_reads_planes(d, op)) return 0;
-    int ta, tb;
-    op_tensors(d, op, ta, tb);
-    const bool x3 = d->plan[op].x6 == 3;
-    int m = ta | tb;
-    for (int t : {DG_TENSOR_X, DG_TENSOR_DY})
-        if ((m & t) && tensor_x3(d, t) != x3) m &= ~t;
-    return m;
-}
-
-// dg_conv_planes_t -> the op's PlaneRefs (out = nullptr when the op takes no planes)
-static int plane_refs(const dg_conv_desc_s *d, int op, const dg_conv_planes_t *p, PlaneRefs &r,
-                      const PlaneRefs *&out) {
-    out = nullptr;
-    if (!p || !op_plane_mask(d, op)) return DG_OK;
+// dg_conv_planes_t -> the op's PlaneRefs in c (c.pr stays NULL when the op takes no planes)
+static int plane_refs(const dg_conv_desc_s *d, int op, const dg_conv_planes_t *p, EngineCall &c) {
+    const int mask = p ? op_plane_mask(d, op) : 0;
+    if (!mask) return DG_OK;
+    PlaneRefs &r = c.refs;
     int ta, tb;
     op_tensors(d, op, ta, tb);
     auto buf = [&](int t) -> void * { return t == DG_TENSOR_X ? p->x : (t == DG_TENSOR_DY ? p->dy : p->w); };
-    const int mask = op_plane_mask(d, op);
     r.a = (mask & ta) ? buf(ta) : nullptr; r.b = (mask & tb) ? buf(tb) : nullptr;
     r.a_ready = (p->ready & ta) != 0; r.b_ready = (p->ready & tb) != 0;
     // a bf16x6 op of a layer with fp16x3 weight planes: the weights' bf16x6 part of the buffer
     if (tb == DG_TENSOR_W && r.b) {
-        if (d->plan[op].x6 == 1 && tensor_x3(d, DG_TENSOR_W)) r.b = (char *)r.b + x3_wbytes(d);
-        r.b_x6 = d->plan[op].x6 == 3 && tensor_reader(d, DG_TENSOR_W, 1);
+        if (d->plan[op].arith == BF16X6 && tensor_x3(d, DG_TENSOR_W)) r.b = (char *)r.b + x3_wbytes(d);
+        r.b_x6 = d->plan[op].arith == F16X3 && tensor_reader(d, DG_TENSOR_W, BF16X6) ? x3_wbytes(d) : 0;
     }
     DG_ARG(((((uintptr_t)r.a) | ((uintptr_t)r.b)) & 15) == 0, "plane buffers must be 16-byte aligned");
-    out = &r;
+    c.pr = &r;
     return DG_OK;
 }
 
@@ -2532,8 +1825,7 @@ int dg_conv_set_act_scale(dg_conv_t d, const float *x_m, const float *x_g, const
 int dg_conv_op_arith(dg_conv_t d, int op, int *arith) {
     DG_ARG(d && arith, "NULL argument");
     DG_ARG(op >= 0 && op < 3, "bad op %d", op);
-    const dg::OpPlan &pl = d->rc[op].on ? d->rc[op].p1 : d->plan[op];
-    *arith = (pl.narrow || pl.co1 || pl.small || pl.ntile) ? DG_MATH_FP32 : pl.x6;
+    *arith = d->rc[op].on ? d->rc[op].p1.arith : d->plan[op].arith;   // (Arith is DG_MATH_*)
     return DG_OK;
 }
 
@@ -2549,14 +1841,14 @@ int dg_conv_fwd_pl(dg_conv_t d, const float *x, int ldx, const float *w, const f
                    dg_stream_t stream) {
     DG_ARG(d && x && w && (y || (planes && planes->out)), "NULL tensor");
     DG_ARG(ldx >= d->Cin && (!y || ldy >= d->Cout), "pixel stride smaller than channels");
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int e = dg::plane_refs(d, DG_OP_FWD, planes, r, pr);
+    dg::EngineCall c;
+    int e = dg::plane_refs(d, DG_OP_FWD, planes, c);
     if (e != DG_OK) return e;
-    return dg::run_engine(d, DG_OP_FWD, x, ldx, w, d->transpose ? 0 : d->Cout, y, ldy, bias, beta, act, alpha, ws,
-                          ws_bytes, (hipStream_t)stream, nullptr, 0, DG_ACT_NONE, 0.f, pr,
-                          planes ? (unsigned short *)planes->out : nullptr, nullptr, nullptr,
-                          planes ? planes->out_format : DG_PLANES_BF16X6);
+    c.A = x; c.lda = ldx; c.B = w; c.ldb = d->transpose ? 0 : d->Cout; c.C = y; c.ldc = ldy;
+    c.bias = bias; c.beta = beta; c.act = act; c.alpha = alpha;
+    c.ws = ws; c.ws_bytes = ws_bytes;
+    if (planes) { c.yp = (unsigned short *)planes->out; c.yp_fmt = planes->out_format; }
+    return dg::run_engine(d, DG_OP_FWD, (hipStream_t)stream, c);
 }
 
 int dg_conv_fwd_pool_ok(dg_conv_t d, int act, int *ok) {
@@ -2575,19 +1867,33 @@ int dg_conv_fwd_pool(dg_conv_t d, const float *x, int ldx, const float *w, const
         dg::set_error("forward plan cannot fuse the max pool (dg_conv_fwd_pool_ok)");
         return DG_ERR_UNSUPPORTED;
     }
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int e = dg::plane_refs(d, DG_OP_FWD, planes, r, pr);
+    dg::EngineCall c;
+    int e = dg::plane_refs(d, DG_OP_FWD, planes, c);
     if (e != DG_OK) return e;
     dg::PoolOut po{pool_idx, pool_y, ldpy, planes ? (unsigned short *)planes->out : nullptr,
                    planes ? planes->out_format : DG_PLANES_BF16X6};
-    return dg::run_engine(d, DG_OP_FWD, x, ldx, w, d->Cout, nullptr, d->Cout, bias, 0.f, act, alpha, ws, ws_bytes,
-                          (hipStream_t)stream, nullptr, 0, DG_ACT_NONE, 0.f, pr, nullptr, &po);
+    c.A = x; c.lda = ldx; c.B = w; c.ldb = d->Cout; c.ldc = d->Cout;
+    c.bias = bias; c.act = act; c.alpha = alpha;
+    c.ws = ws; c.ws_bytes = ws_bytes;
+    c.po = &po;
+    return dg::run_engine(d, DG_OP_FWD, (hipStream_t)stream, c);
 }
 
 int dg_conv_fwd(dg_conv_t d, const float *x, int ldx, const float *w, const float *bias, float *y, int ldy,
                 float beta, int act, float alpha, void *ws, size_t ws_bytes, dg_stream_t stream) {
     return dg_conv_fwd_pl(d, x, ldx, w, bias, y, ldy, beta, act, alpha, nullptr, ws, ws_bytes, stream);
+}
+
+// an input gradient: c carries the entry point's mask
+static int bwd_data(dg_conv_t d, const float *dy, int lddy, const float *w, float *dx, int lddx, float beta,
+                    const dg_conv_planes_t *planes, void *ws, size_t ws_bytes, dg_stream_t stream, dg::EngineCall &c) {
+    int e = dg::plane_refs(d, DG_OP_BWD_DATA, planes, c);
+    if (e != DG_OK) return e;
+    c.A = dy; c.lda = lddy; c.B = w; c.ldb = d->transpose ? d->g.Co : 0; c.C = dx; c.ldc = lddx;
+    c.beta = beta;
+    c.ws = ws; c.ws_bytes = ws_bytes;
+    if (planes) { c.yp = (unsigned short *)planes->out; c.yp_fmt = planes->out_format; }
+    return dg::run_engine(d, DG_OP_BWD_DATA, (hipStream_t)stream, c);
 }
 
 int dg_conv_bwd_data_pl(dg_conv_t d, const float *dy, int lddy, const float *w, float *dx, int lddx, float beta,
@@ -2597,14 +1903,9 @@ int dg_conv_bwd_data_pl(dg_conv_t d, const float *dy, int lddy, const float *w, 
     DG_ARG(lddy >= d->Cout && lddx >= d->Cin, "pixel stride smaller than channels");
     DG_ARG(!z || ldz >= d->Cin, "pixel stride smaller than channels");
     DG_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "unknown activation %d", act);
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int e = dg::plane_refs(d, DG_OP_BWD_DATA, planes, r, pr);
-    if (e != DG_OK) return e;
-    return dg::run_engine(d, DG_OP_BWD_DATA, dy, lddy, w, d->transpose ? d->g.Co : 0, dx, lddx, nullptr, beta,
-                          DG_ACT_NONE, 0.f, ws, ws_bytes, (hipStream_t)stream, z, z ? ldz : 0,
-                          z ? act : DG_ACT_NONE, alpha, pr, planes ? (unsigned short *)planes->out : nullptr, nullptr,
-                          nullptr, planes ? planes->out_format : DG_PLANES_BF16X6);
+    dg::EngineCall c;
+    c.mz = z; c.ldmz = z ? ldz : 0; c.mact = z ? act : DG_ACT_NONE; c.malpha = alpha;
+    return bwd_data(d, dy, lddy, w, dx, lddx, beta, planes, ws, ws_bytes, stream, c);
 }
 
 int dg_conv_bwd_data_masked_sum(dg_conv_t d, const float *dy, int lddy, const float *w, float *dx, int lddx,
@@ -2613,14 +1914,9 @@ int dg_conv_bwd_data_masked_sum(dg_conv_t d, const float *dy, int lddy, const fl
     DG_ARG(d && dy && w && dx && z, "NULL tensor");
     DG_ARG(lddy >= d->Cout && lddx >= d->Cin && ldz >= d->Cin, "pixel stride smaller than channels");
     DG_ARG(act >= DG_ACT_NONE && act <= DG_ACT_SIGMOID, "unknown activation %d", act);
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int e = dg::plane_refs(d, DG_OP_BWD_DATA, planes, r, pr);
-    if (e != DG_OK) return e;
-    return dg::run_engine(d, DG_OP_BWD_DATA, dy, lddy, w, d->transpose ? d->g.Co : 0, dx, lddx, nullptr, beta,
-                          DG_ACT_NONE, 0.f, ws, ws_bytes, (hipStream_t)stream, z, ldz, act | dg::DG_MASK_SUM, alpha,
-                          pr, planes ? (unsigned short *)planes->out : nullptr, nullptr, nullptr,
-                          planes ? planes->out_format : DG_PLANES_BF16X6);
+    dg::EngineCall c;
+    c.mz = z; c.ldmz = ldz; c.mact = act | dg::DG_MASK_SUM; c.malpha = alpha;
+    return bwd_data(d, dy, lddy, w, dx, lddx, beta, planes, ws, ws_bytes, stream, c);
 }
 
 int dg_conv_bwd_data_xmask(dg_conv_t d, const float *dy, int lddy, const float *w, float *dx, int lddx, float beta,
@@ -2631,14 +1927,9 @@ int dg_conv_bwd_data_xmask(dg_conv_t d, const float *dy, int lddy, const float *
     DG_ARG((((uintptr_t)planes->x) & 7) == 0, "x planes must be 8-byte aligned");
     DG_ARG(lddy >= d->Cout && lddx >= d->Cin, "pixel stride smaller than channels");
     DG_ARG(d->Cin % 16 == 0, "x planes need Cin %% 16 == 0");
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int e = dg::plane_refs(d, DG_OP_BWD_DATA, planes, r, pr);
-    if (e != DG_OK) return e;
-    return dg::run_engine(d, DG_OP_BWD_DATA, dy, lddy, w, d->transpose ? d->g.Co : 0, dx, lddx, nullptr, beta,
-                          DG_ACT_NONE, 0.f, ws, ws_bytes, (hipStream_t)stream, nullptr, 0, act, alpha, pr,
-                          (unsigned short *)planes->out, nullptr, (const unsigned short *)planes->x,
-                          planes->out_format);
+    dg::EngineCall c;
+    c.mact = act; c.malpha = alpha; c.mzp = (const unsigned short *)planes->x;
+    return bwd_data(d, dy, lddy, w, dx, lddx, beta, planes, ws, ws_bytes, stream, c);
 }
 
 int dg_conv_bwd_data(dg_conv_t d, const float *dy, int lddy, const float *w, float *dx, int lddx, float beta,
@@ -2665,18 +1956,16 @@ int dg_conv_bwd_filter_pl(dg_conv_t d, const float *x, int ldx, const float *dy,
     DG_ARG(ldx >= d->Cin && lddy >= d->Cout, "pixel stride smaller than channels");
     const dg::OpPlan &pl = d->plan[DG_OP_BWD_FILTER];
     DG_ARG(ws_bytes >= pl.ws_bytes && ws != nullptr, "workspace too small: need %zu bytes", pl.ws_bytes);
-    size_t slab_bytes = pl.colsum_off;
-    dg::PlaneRefs r{};
-    const dg::PlaneRefs *pr;
-    int rc = dg::plane_refs(d, DG_OP_BWD_FILTER, planes, r, pr);
+    dg::EngineCall c;
+    int rc = dg::plane_refs(d, DG_OP_BWD_FILTER, planes, c);
     if (rc != DG_OK) return rc;
     // conv view: A = conv input, B = conv output grad
-    if (!d->transpose)
-        rc = dg::run_engine(d, DG_OP_BWD_FILTER, x, ldx, dy, lddy, dw, d->g.Co, nullptr, beta, DG_ACT_NONE, 0.f, ws,
-                            slab_bytes, (hipStream_t)stream, nullptr, 0, DG_ACT_NONE, 0.f, pr);
-    else
-        rc = dg::run_engine(d, DG_OP_BWD_FILTER, dy, lddy, x, ldx, dw, d->g.Co, nullptr, beta, DG_ACT_NONE, 0.f, ws,
-                            slab_bytes, (hipStream_t)stream, nullptr, 0, DG_ACT_NONE, 0.f, pr);
+    if (!d->transpose) { c.A = x; c.lda = ldx; c.B = dy; c.ldb = lddy; }
+    else { c.A = dy; c.lda = lddy; c.B = x; c.ldb = ldx; }
+    c.C = dw; c.ldc = d->g.Co;
+    c.beta = beta;
+    c.ws = ws; c.ws_bytes = pl.colsum_off;   // (the bias partials follow the GEMM's part)
+    rc = dg::run_engine(d, DG_OP_BWD_FILTER, (hipStream_t)stream, c);
     if (rc != DG_OK) return rc;
     if (dbias) {
         long M = (long)d->N * d->Ho * d->Wo;

@@ -1,5 +1,6 @@
 // Shared device-side definitions of the conv engine (conv.hip: fp32 MFMA
-// kernels, planner and C ABI; conv_x6.hip: the bf16x6 split-precision kernel).
+// kernels, launch and C ABI; conv_plan.hip: the planner; conv_x6.hip: the bf16x6
+// split-precision kernel).
 #pragma once
 #include "common.h"
 
@@ -409,8 +410,10 @@ __device__ __forceinline__ void conv_epilogue32(const GemmArgs &p, f32x16 (&acc)
     if (p.ymax) block_atomic_absmax(p.ymax, vmax);
 }
 
-// launcher of the bf16x6 kernels (conv_x6.hip); cfg indexes kX6Cfgs
-void launch_gemm_x6(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
+// launchers of the implicit-GEMM plane kernels (conv_x6.hip); cfg indexes the arithmetic's tile list
+// (conv_tiles.h: DG_TILES_X6 for bf16x6 and fp16, DG_TILES_X3); an unknown cfg sets the library
+// error and returns DG_ERR_ARG
+int launch_gemm_x6(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
 // the halo-tiled bf16x6 kernel (conv_x6h.hip): kt 3 = stride-1 3x3 FWD / DGRAD, kt 2 = the
 // sub-pixel phases of a stride-2 4x4 DGRAD (grid y = phase * splits + split); bn = 64 | 128.
 // ni 3 bf16x6, 2 fp16 (DG_MATH_FP16), 4 fp16x3 (kt 3, bn 64 | 128; kt 2 phases; kt 4 stride-1 4x4
@@ -434,13 +437,13 @@ void launch_weight_bound(const float *w, long K, int Co, const float *bias, floa
 // max over input channels of sum over taps and output channels of |w[tap][ci][co]| into gout[0]
 // (dg_weight_bound_in)
 void launch_weight_bound_in(const float *w, int taps, int Ci, int Co, float *gout, hipStream_t s);
-// the fp16 conv math (DG_MATH_FP16): one fp16 plane [rows][C] and its GEMM (kF16Cfgs)
+// the fp16 conv math (DG_MATH_FP16): one fp16 plane [rows][C] and its GEMM
 void launch_split_f16(const float *src, int ld, long rows, int C, void *dst, hipStream_t s);
 void launch_split_f16_pair(const float *a, int lda, long ra, int ca, void *da, const float *b, int ldb, long rb,
                            int cb, void *db, hipStream_t s);
-void launch_gemm_f16(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
-// fp16x3 (DG_MATH_F16X3) generic GEMM: kX3Cfgs tiles, NI = 4 images per K-tile of 32
-void launch_gemm_x3(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
+int launch_gemm_f16(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
+// fp16x3 (DG_MATH_F16X3) generic GEMM: NI = 4 images per K-tile of 32
+int launch_gemm_x3(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s);
 // small-Cin 4x4 stride-2 FWD / WGRAD on fp32 MFMA (conv_small.hip)
 bool small_conv_ok(const ConvGeom &g, int mode, int lda);
 int small_wgrad_rows_per_block(const ConvGeom &g);

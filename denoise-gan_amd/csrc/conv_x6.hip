@@ -29,6 +29,7 @@
 //   transposed (ds_read_b64_tr_b16).
 // The epilogue is staged through LDS (conv_impl.h conv_epilogue16).
 #include "conv_x6.h"
+#include "conv_tiles.h"
 #include <algorithm>
 
 namespace dg {
@@ -895,63 +896,49 @@ void launch_split_f16(const float *src, int ld, long rows, int C, void *dst, hip
     hipLaunchKernelGGL(k_split_f16, dim3(blocks), dim3(256), 0, s, src, ld, rows, C, (_Float16 *)dst);
 }
 
-// tile configs of the bf16x6 (ni 3) and fp16 (ni 2) kernels (index = kX6Cfgs / kF16Cfgs in conv.hip)
+// the bf16x6 (ni 3) and fp16 (ni 2) kernels on the tiles of DG_TILES_X6 (conv_tiles.h)
 template <int NI>
-static void launch_gemm_planes(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
-#define DG_X6(C, BM_, BN_, WM_, WN_, MW_, NB_)                                                                  \
+static int launch_gemm_planes(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
+#define DG_X6(C, BM_, BN_, WM_, WN_, BK_, MW_, NB_, BPC_, EFF_)                                                 \
     case C: {                                                                                                   \
         const dim3 blk(64 * WM_ * WN_);                                                                         \
         if (mode == MODE_FWD) hipLaunchKernelGGL((k_conv_gemm_x6<MODE_FWD, BM_, BN_, WM_, WN_, MW_, NB_, NI>), grid, blk, 0, s, a); \
         else if (mode == MODE_DGRAD) hipLaunchKernelGGL((k_conv_gemm_x6<MODE_DGRAD, BM_, BN_, WM_, WN_, MW_, NB_, NI>), grid, blk, 0, s, a); \
         else hipLaunchKernelGGL((k_conv_gemm_x6<MODE_WGRAD, BM_, BN_, WM_, WN_, MW_, NB_, NI>), grid, blk, 0, s, a); \
-        break;                                                                                                  \
+        return DG_OK;                                                                                           \
     }
     switch (cfg) {
-        DG_X6(0, 128, 128, 2, 2, 2, 3)
-        DG_X6(1, 128, 64, 2, 2, 2, 3)
-        DG_X6(2, 64, 128, 2, 2, 2, 3)
-        DG_X6(3, 64, 64, 2, 2, 3, 3)
-        DG_X6(4, 256, 128, 4, 2, 2, 3)
-        DG_X6(5, 128, 256, 2, 4, 2, 3)
-        DG_X6(6, 128, 32, 4, 1, 3, 3)
+        DG_TILES_X6(DG_X6)
+    default:
+        set_error("%s conv GEMM: no tile config %d", NI == 2 ? "fp16" : "bf16x6", cfg);
+        return DG_ERR_ARG;
     }
 #undef DG_X6
 }
 
-void launch_gemm_x6(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
-    launch_gemm_planes<3>(mode, cfg, grid, a, s);
+int launch_gemm_x6(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
+    return launch_gemm_planes<3>(mode, cfg, grid, a, s);
 }
 
-void launch_gemm_f16(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
-    launch_gemm_planes<2>(mode, cfg, grid, a, s);
+int launch_gemm_f16(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
+    return launch_gemm_planes<2>(mode, cfg, grid, a, s);
 }
 
-// fp16x3 tile configs (index = kX3Cfgs in conv.hip): four 16-wide images per K-tile of
-// 32, so the 128-wide tiles keep one K-tile ahead in two LDS buffers (67 KB at 128 x 128:
-// two blocks per CU), the narrow ones two ahead in three
-void launch_gemm_x3(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
-#define DG_X3(C, BM_, BN_, WM_, WN_, MW_, NB_)                                                                  \
+// the fp16x3 kernel (ni 4) on the tiles of DG_TILES_X3 (conv_tiles.h)
+int launch_gemm_x3(int mode, int cfg, dim3 grid, const GemmArgs &a, hipStream_t s) {
+#define DG_X3(C, BM_, BN_, WM_, WN_, BK_, MW_, NB_, BPC_, EFF_)                                                 \
     case C: {                                                                                                   \
         const dim3 blk(64 * WM_ * WN_);                                                                         \
         if (mode == MODE_FWD) hipLaunchKernelGGL((k_conv_gemm_x6<MODE_FWD, BM_, BN_, WM_, WN_, MW_, NB_, 4>), grid, blk, 0, s, a); \
         else if (mode == MODE_DGRAD) hipLaunchKernelGGL((k_conv_gemm_x6<MODE_DGRAD, BM_, BN_, WM_, WN_, MW_, NB_, 4>), grid, blk, 0, s, a); \
         else hipLaunchKernelGGL((k_conv_gemm_x6<MODE_WGRAD, BM_, BN_, WM_, WN_, MW_, NB_, 4>), grid, blk, 0, s, a); \
-        break;                                                                                                  \
+        return DG_OK;                                                                                           \
     }
-#ifndef DG_X3_NB0
-#define DG_X3_NB0 2
-#endif
-#ifndef DG_X3_NB12
-#define DG_X3_NB12 2
-#endif
     switch (cfg) {
-        DG_X3(0, 128, 128, 2, 2, 2, DG_X3_NB0)
-        DG_X3(1, 128, 64, 2, 2, 2, DG_X3_NB12)
-        DG_X3(2, 64, 128, 2, 2, 2, DG_X3_NB12)
-        DG_X3(3, 64, 64, 2, 2, 3, 3)
-        DG_X3(4, 256, 128, 4, 2, 1, 2)
-        DG_X3(5, 128, 256, 2, 4, 1, 2)
-        DG_X3(6, 128, 32, 4, 1, 3, 3)
+        DG_TILES_X3(DG_X3)
+    default:
+        set_error("fp16x3 conv GEMM: no tile config %d", cfg);
+        return DG_ERR_ARG;
     }
 #undef DG_X3
 }

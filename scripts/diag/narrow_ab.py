@@ -3,7 +3,8 @@
 SR family's narrow layers at their BASELINE batch sizes: the thread-per-pixel
 k_narrow_fwd_px (default) vs the wave-per-pixel k_narrow_fwd
 (DG_PLAN_DISABLE=narrow_px).  HIP events, median of reps, alternating A/B
-rounds.  Sets csrc/conv.hip NFWD_PX_MIN_M."""
+rounds.  Sets csrc/conv.hip NFWD_PX_MIN_M (the launch-time choice in run_engine; the planner is
+csrc/conv_plan.hip)."""
 import os
 import sys
 

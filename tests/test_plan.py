@@ -1,6 +1,6 @@
 """Host-side planner choices for the bs16 training step's conv layers (no GPU:
 descriptors are planned at creation).  Pins the kernel family each pix2pix
-layer op runs on (csrc/conv.hip make_plan / plan_recast, printed under
+layer op runs on (csrc/conv_plan.hip make_plan / plan_recast, printed under
 DG_PLAN_DEBUG), so a planner change that silently moves a layer back to a
 slower path shows up here; the GPU tests hold every path to the fp64 bar."""
 import os
@@ -72,6 +72,26 @@ def test_plan_kernel_family(layer, expect):
             got.setdefault(mode, kind)
     for mode, kind in expect.items():
         assert got.get(mode) == kind, (layer, got)
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libdgan.so not built")
+def test_plan_snapshot():
+    """The planner as a whole: every layer geometry of the benchmarked networks, of full-width
+    inference and of the GPU conv tests, under each of the four maths, plans exactly what
+    tests/plan_snapshot.json records (scripts/gen_plan_snapshot.py: the [dg plan] lines, workspace
+    sizes, arithmetic, plane masks / sizes / formats, pool fusability).  A planner change that
+    moves any layer to another kernel, tile or split count regenerates the file, and the diff
+    shows which layers moved."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("gen_plan_snapshot",
+                                                  os.path.join(REPO, "scripts", "gen_plan_snapshot.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(gen.SNAPSHOT) as f:
+        want = gen.unpack(json.load(f))
+    diff = gen.differences(want, gen.record())
+    assert not diff, "\n".join(diff[:40])
 
 
 CSRC = os.path.join(REPO, "denoise-gan_amd", "csrc")
