@@ -42,7 +42,19 @@
 
 // fp16x3 kernel (conv_x6.hip k_conv_gemm_x6, NI 4): four 16-wide images per K-tile of 32, so
 // the 128-wide tiles keep one K-tile ahead in two LDS buffers (67 KB at 128 x 128: two blocks
-// per CU), the narrow ones two ahead in three
+// per CU), the narrow ones two ahead in three.  The 8-wave tiles (4, 5) run the two-half K loop
+// (conv_x6.hip ktile_w8), which needs a third buffer: a tile's buffer lives until the later
+// half has read it (149,760 B at 128 x 256, one block per CU either way); DG_X3_W8_LOCKSTEP
+// builds the lock-step loop on two buffers for A/B runs.  Their eff values are those fitted on
+// the lock-step loop: the two-half loop runs the filter gradients 21 % faster (profiles/w8), but
+// a lower eff would move plans of tests/plan_snapshot.json, so the planner keeps the old cost
+#ifndef DG_X3_NB45
+#ifdef DG_X3_W8_LOCKSTEP
+#define DG_X3_NB45 2
+#else
+#define DG_X3_NB45 3
+#endif
+#endif
 #ifndef DG_X3_NB0
 #define DG_X3_NB0 2
 #endif
@@ -54,6 +66,6 @@
     X(1, 128, 64, 2, 2, 32, 2, DG_X3_NB12, 3, 1.15)                                              \
     X(2, 64, 128, 2, 2, 32, 2, DG_X3_NB12, 3, 1.15)                                              \
     X(3, 64, 64, 2, 2, 32, 3, 3, 3, 1.40)                                                        \
-    X(4, 256, 128, 4, 2, 32, 1, 2, 1, 1.00)                                                      \
-    X(5, 128, 256, 2, 4, 32, 1, 2, 1, 0.90)                                                      \
+    X(4, 256, 128, 4, 2, 32, 1, DG_X3_NB45, 1, 1.00)                                             \
+    X(5, 128, 256, 2, 4, 32, 1, DG_X3_NB45, 1, 0.90)                                             \
     X(6, 128, 32, 4, 1, 32, 3, 3, 2, 1.45)

@@ -31,6 +31,7 @@
 #include "conv_x6.h"
 #include "conv_tiles.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace dg {
 
@@ -133,6 +134,13 @@ k_conv_gemm_x6(const GemmArgs p) {
     constexpr int BUF = NI * (APL + BPL);           // bytes per buffer
     constexpr int NW_ = WGM * WGN;
     static_assert(WGM * WGN == 4 || WGM * WGN == 8, "4 or 8 waves");
+    // the 8-wave fp16x3 tiles run the two-half K loop (pipeline_w8 below)
+#ifdef DG_X3_W8_LOCKSTEP
+    constexpr bool W8 = false;
+#else
+    constexpr bool W8 = X3 && NW_ == 8;
+    static_assert(!W8 || NBUF == 3, "the two-half loop runs on three LDS buffers");
+#endif
     static_assert(TM >= 1 && TN >= 1 && WTM % 16 == 0 && WTN % 16 == 0, "wave tile of 16x16 tiles");
     static_assert(BM % 32 == 0 && BN % 32 == 0 && BM <= 256 && BN <= 256, "tile");
 
@@ -329,8 +337,11 @@ k_conv_gemm_x6(const GemmArgs p) {
     // WGRAD: output pixel -> (n, ho, wo) by multiply-shift division
     auto fdiv = [](unsigned n, unsigned mul, int shr) __attribute__((always_inline)) { return (__umulhi(n, mul) + n) >> shr; };
 
-    // issue the DMA of the K-tile at k0 (the walker's tile) into LDS buffer sm
-    auto issue_tile = [&](int k0, char *sm) __attribute__((always_inline)) {
+    // issue the DMA of the K-tile at k0 (the walker's tile) into LDS buffer sm.  The two-half
+    // loop splits it: phase 1 only computes the NMINE source offsets into o (an out-of-range one
+    // for a dead slot) and advances the walker, phase 2 only fires the DMAs from o; phase 0 is both
+    auto issue_phase = [&](int k0, char *sm, auto phc, unsigned *o) __attribute__((always_inline)) {
+        constexpr int PH = decltype(phc)::value;
         char *As = sm;
         char *Bs = As + NI * APL;
         // wave-uniform parts of this K-tile's offsets (tap (wk_a, wk_b) of chunk wk_chunk)
@@ -351,6 +362,14 @@ k_conv_gemm_x6(const GemmArgs p) {
         // a tile past this block's K range (the pipeline's tail) is issued out of range:
         // same DMA count, zeros, no memory traffic (WGRAD tests pix < kend per row)
         const bool live = MODE == MODE_WGRAD || k0 < kend;
+        // WGRAD A slots of the two-half loop: with NW a multiple of the BM / 32 blocks of a plane
+        // image, slot j is the same block of plane (wid + NW j) / per -- the same k-row, columns
+        // and (plane & 1) pixel half as slot j - WSH, one piece (plane >> 1) further -- so it takes
+        // that slot's pixel test and offset plus the pieces' distance instead of two more divisions
+        constexpr int WSH = (W8 && MODE == MODE_WGRAD && A_ALL && NW % (BM / 32) == 0)
+                                ? ((NW / (BM / 32)) % 2 == 0 ? 1 : 2) : 0;
+        unsigned aoff[A_NJ];
+        bool aok[A_NJ];
 #pragma unroll
         for (int j = 0; j < A_NJ; ++j) {
             const int d = asl[j].live ? wid + NW * j : 0, per = BM / 32;
@@ -360,6 +379,9 @@ k_conv_gemm_x6(const GemmArgs p) {
             if constexpr (MODE != MODE_WGRAD) {
                 ok = (amask[j] >> tap_bit) & 1;
                 off = (unsigned)(abase[j] + a_delta);
+            } else if (WSH > 0 && j >= WSH) {
+                ok = aok[j - WSH];
+                off = aoff[j - WSH] + 2u * (unsigned)(wg_ci[j] - wg_ci[j - WSH]);
             } else {
                 const unsigned pix = (unsigned)(k0 + asl[j].r + (X6 ? 0 : 16 * (X3 ? asl[j].plane & 1 : asl[j].plane)));
                 const unsigned t = fdiv(pix, p.mg_wo, p.sh_wo); const int wo = (int)(pix - t * g.Wo);
@@ -368,7 +390,10 @@ k_conv_gemm_x6(const GemmArgs p) {
                 ok = arow_n[j] >= 0 && (int)pix < kend && (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
                 off = ((unsigned)(((int)n * g.H + hi) * g.W + wi) * (RM * p.lda) + wg_ci[j]) * 2u;
             }
-            dma(rA, dst, ok && live ? off : DG_OOB);
+            aok[j] = ok; aoff[j] = off;
+            if constexpr (PH == 0) dma(rA, dst, ok && live ? off : DG_OOB);
+            else if constexpr (PH == 1) o[j] = ok && live ? off : DG_OOB;
+            else dma(rA, dst, o[j]);
         }
 #pragma unroll
         for (int j = 0; j < B_NJ; ++j) {
@@ -390,9 +415,14 @@ k_conv_gemm_x6(const GemmArgs p) {
                     : X3 ? ((unsigned)pix * (2 * p.ldb) + (col >> 5) * 64 + 32 * (bsl[j].plane >> 1) + (col & 31)) * 2u
                          : ((unsigned)pix * p.ldb + col) * 2u;
             }
-            dma(rB, dst, ok && live ? off : DG_OOB);
+            if constexpr (PH == 0) dma(rB, dst, ok && live ? off : DG_OOB);
+            else if constexpr (PH == 1) o[A_NJ + j] = ok && live ? off : DG_OOB;
+            else dma(rB, dst, o[A_NJ + j]);
         }
-        if constexpr (MODE != MODE_WGRAD) walk_next();
+        if constexpr (MODE != MODE_WGRAD && PH != 2) walk_next();
+    };
+    auto issue_tile = [&](int k0, char *sm) __attribute__((always_inline)) {
+        issue_phase(k0, sm, std::integral_constant<int, 0>{}, nullptr);
     };
     // barrier without the vmcnt(0) drain of __syncthreads (DMAs stay in flight)
     auto barrier = []() __attribute__((always_inline)) {
@@ -459,46 +489,84 @@ k_conv_gemm_x6(const GemmArgs p) {
     constexpr bool MIDB = true;
 #endif
     constexpr int DIST = MIDB ? NBUF : AHEAD;
+    // Timing-only ablations of the 8-wave fp16x3 K-tile (wrong results; profiles/w8/*_segments.txt):
+    // DG_X3_ABL bit 0 drops the MFMAs (the fragments stay live), bit 1 the DMA issue with its
+    // address math, bit 2 the fragment reads (the MFMAs run on undefined registers)
+#ifndef DG_X3_ABL
+#define DG_X3_ABL 0
+#endif
+    constexpr int ABL = (X3 && NW_ == 8) ? DG_X3_ABL : 0;
+    // fp16x3: A [h | h'] / [l | l'] of k 0..15 | 16..31; B the same pairs (KC
+    // weights of DGRAD: images 0,2 = h, 1,3 = l); h.h', l.h', h.l'
+    auto x3_read = [&](const char *cur, f16x8 (&ah)[TM], f16x8 (&al)[TM], f16x8 (&bh)[TN],
+                       f16x8 (&bl)[TN]) __attribute__((always_inline)) {
+        if constexpr ((ABL & 4) != 0) {
+#pragma unroll
+            for (int a = 0; a < TM; ++a) asm volatile("" : "=v"(ah[a]), "=v"(al[a]));
+#pragma unroll
+            for (int b = 0; b < TN; ++b) asm volatile("" : "=v"(bh[b]), "=v"(bl[b]));
+            return;
+        }
+        const char *B0 = cur + 4 * APL;
+#pragma unroll
+        for (int a = 0; a < TM; ++a) {
+            const int r0 = wm * WTM + a * 16;
+            ah[a] = __builtin_bit_cast(f16x8, frag(cur, cur + APL, r0, A_KC, true));
+            al[a] = __builtin_bit_cast(f16x8, frag(cur + 2 * APL, cur + 3 * APL, r0, A_KC, true));
+        }
+        constexpr int BH1 = B_KC ? 2 : 1, BL0 = B_KC ? 1 : 2;
+#pragma unroll
+        for (int b = 0; b < TN; ++b) {
+            const int c0 = wn * WTN + b * 16;
+            bh[b] = __builtin_bit_cast(f16x8, frag(B0, B0 + BH1 * BPL, c0, B_KC, false));
+            bl[b] = __builtin_bit_cast(f16x8, frag(B0 + BL0 * BPL, B0 + 3 * BPL, c0, B_KC, false));
+        }
+    };
+    auto x3_mfma = [&](const f16x8 (&ah)[TM], const f16x8 (&al)[TM], const f16x8 (&bh)[TN],
+                       const f16x8 (&bl)[TN]) __attribute__((always_inline)) {
+        if constexpr ((ABL & 1) != 0) {
+#pragma unroll
+            for (int a = 0; a < TM; ++a) asm volatile("" ::"v"(ah[a]), "v"(al[a]));
+#pragma unroll
+            for (int b = 0; b < TN; ++b) asm volatile("" ::"v"(bh[b]), "v"(bl[b]));
+            return;
+        }
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bh[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bh[b], acc[a][b], 0, 0, 0);
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+                acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bl[b], acc[a][b], 0, 0, 0);
+    };
+    auto x3_issue = [&](int k0, char *sm) __attribute__((always_inline)) {
+        if constexpr ((ABL & 2) == 0) issue_tile(k0, sm);
+    };
+    auto x3_offs = [&](int k0, unsigned (&o)[NMINE]) __attribute__((always_inline)) {
+        if constexpr ((ABL & 2) == 0) issue_phase(k0, nullptr, std::integral_constant<int, 1>{}, o);
+    };
+    auto x3_fire = [&](char *sm, unsigned (&o)[NMINE]) __attribute__((always_inline)) {
+        if constexpr ((ABL & 2) == 0) issue_phase(0, sm, std::integral_constant<int, 2>{}, o);
+    };
     auto ktile = [&](int kt, const char *cur, char *nxt) __attribute__((always_inline)) {
         if constexpr (X3) {
-            // fp16x3: A [h | h'] / [l | l'] of k 0..15 | 16..31; B the same pairs (KC
-            // weights of DGRAD: images 0,2 = h, 1,3 = l); h.h', l.h', h.l'
             f16x8 ah[TM], al[TM], bh[TN], bl[TN];
-            const char *B0 = cur + 4 * APL;
-#pragma unroll
-            for (int a = 0; a < TM; ++a) {
-                const int r0 = wm * WTM + a * 16;
-                ah[a] = __builtin_bit_cast(f16x8, frag(cur, cur + APL, r0, A_KC, true));
-                al[a] = __builtin_bit_cast(f16x8, frag(cur + 2 * APL, cur + 3 * APL, r0, A_KC, true));
-            }
-            constexpr int BH1 = B_KC ? 2 : 1, BL0 = B_KC ? 1 : 2;
-#pragma unroll
-            for (int b = 0; b < TN; ++b) {
-                const int c0 = wn * WTN + b * 16;
-                bh[b] = __builtin_bit_cast(f16x8, frag(B0, B0 + BH1 * BPL, c0, B_KC, false));
-                bl[b] = __builtin_bit_cast(f16x8, frag(B0 + BL0 * BPL, B0 + 3 * BPL, c0, B_KC, false));
-            }
+            x3_read(cur, ah, al, bh, bl);
             if constexpr (MIDB) {
                 barrier();
-                issue_tile(kbeg + (kt + DIST) * BK, const_cast<char *>(cur));
+                x3_issue(kbeg + (kt + DIST) * BK, const_cast<char *>(cur));
             } else {
-                issue_tile(kbeg + (kt + AHEAD) * BK, nxt);
+                x3_issue(kbeg + (kt + AHEAD) * BK, nxt);
             }
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bh[b], acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[a], bh[b], acc[a][b], 0, 0, 0);
-#pragma unroll
-            for (int a = 0; a < TM; ++a)
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[a], bl[b], acc[a][b], 0, 0, 0);
+            x3_mfma(ah, al, bh, bl);
             wait_dma_c<(DIST - 1) * NMINE>();
             barrier();
             return;
@@ -544,12 +612,96 @@ k_conv_gemm_x6(const GemmArgs p) {
         wait_dma_c<(DIST - 1) * NMINE>();
         barrier();
     };
+    // The two-half K loop of the 8-wave fp16x3 tiles (DG_TILES_X3 rows 4, 5; MI355X: the two waves
+    // of a SIMD share one matrix pipe, so eight waves in lock step idle it while they all load and
+    // queue for it while they all compute).  Waves 0-3 (half 0) and 4-7 (half 1; wid >> 2, the
+    // usual SIMD partners -- a pairing for speed only, every barrier is the workgroup's) run half a
+    // K-tile apart.  A wave's K-tile t is two segments, each closed by one s_barrier:
+    //   L(t)  issue this wave's DMAs of tile t + 2 into buffer (t + 2) % 3, read the fragments of
+    //         tile t from buffer t % 3 into registers, s_waitcnt vmcnt(NMINE) (its DMAs of tile
+    //         t + 1 have landed; those of t + 2 stay in flight), lgkmcnt(0), s_barrier
+    //   C(t)  the 48 MFMAs of tile t (h.h', l.h', h.l' as in the lock-step loop: same sums, same
+    //         order, bit-identical results) with the source offsets of tile t + 3 (registers only)
+    //         computed in their issue gaps, s_barrier
+    // Half 1 crosses one extra barrier before its loop and half 0 one after, so with segment s
+    // the interval between barriers s - 1 and s (barrier -1 = P below):
+    //   half 0: L(t) = segment 2t,     C(t) = segment 2t + 1
+    //   half 1: L(t) = segment 2t + 1, C(t) = segment 2t + 2     (segment 0 / 2nk: the idle one)
+    // and a SIMD's pipe runs one half's MFMAs beside the other half's reads, DMAs and address math.
+    //
+    // Sync ledger (three buffers; tile T lives in buffer T % 3, T >= 0):
+    //   DMA landed -> any wave's read.  Tile T >= 1 is read in segments 2T (half 0) and 2T + 1.
+    //     Each wave retires its own DMAs of tile T by the vmcnt(NMINE) of L(T - 1), segments
+    //     2T - 2 / 2T - 1 (issue order: tile T in L(T - 2) or the prologue, tile T + 1 in L(T - 1)
+    //     before the wait; loads retire in order); barrier 2T - 1 follows both halves' waits and
+    //     precedes both reads, so a buffer is read at least one segment after the wait that
+    //     retires it.  Tile 0: the prologue's vmcnt(NMINE) and barrier P.
+    //   last read by either half -> refill.  Buffer T % 3 is last read in segment 2T + 1 (half 1's
+    //     L(T)); the reads have returned by the lgkmcnt(0) in front of barrier 2T + 1.  Its refill,
+    //     tile T + 3, is issued in L(T + 1), segments 2T + 2 / 2T + 3, both after barrier 2T + 1.
+    //     Tiles 0..2 fill fresh buffers; tiles >= nk are issued out of range (zeros, no traffic)
+    //     so every count above is compile-time.  The offsets o[] a load segment fires are plain
+    //     registers of the wave (tile 2's from the prologue, tile t + 3's from C(t)): no sync.
+    //   epilogue.  vmcnt(0) and one more barrier after both loops before smem0 is reused.
+    //   s_barrier per wave = P + skew/unskew + 2 nk + epilogue = 2 nk + 3 in BOTH halves (half 1
+    //     skews before the loop, half 0 unskews after it; the loop trip count nk is the block's):
+    //     nk 1: 5 / 5, nk 2: 7 / 7, nk 3: 9 / 9, nk 4: 11 / 11, nk 5: 13 / 13.
+    // DG_X3_W8_LOCKSTEP builds the lock-step loop above for these tiles (conv_tiles.h: on two
+    // buffers) for A/B runs.
+    auto ktile_w8 = [&](int kt, const char *cur, char *nxt, unsigned (&o)[NMINE]) __attribute__((always_inline)) {
+        // L(t): the DMAs of tile t + 2 from the offsets o of the last compute segment, then the reads
+        x3_fire(nxt, o);
+        __builtin_amdgcn_sched_barrier(0);
+        f16x8 ah[TM], al[TM], bh[TN], bl[TN];
+        x3_read(cur, ah, al, bh, bl);
+        wait_dma_c<NMINE>();
+        barrier();
+        __builtin_amdgcn_sched_barrier(0);   // (no MFMA up into the load segment)
+        // C(t): the MFMAs, and between them -- the pipe takes one per 16 cycles from this wave, the
+        // issue slots between are free -- the offsets of tile t + 3 for L(t + 1): the load segment,
+        // the longer of the two (profiles/w8), keeps only the DMA issue and the reads.  The first
+        // 16 MFMAs go alone (VALU at the head of a compute segment stalls the younger wave)
+        x3_offs(kbeg + (kt + 3) * BK, o);
+        x3_mfma(ah, al, bh, bl);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x006, 3, 0);   // VALU / SALU
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        barrier();
+    };
+    auto pipeline_w8 = [&](char *L0, char *L1, char *L2) __attribute__((always_inline)) {
+        const int half = wid >> 2;
+        unsigned o[NMINE] = {};
+        x3_issue(kbeg, L0);
+        x3_issue(kbeg + BK, L1);
+        x3_offs(kbeg + 2 * BK, o);
+        wait_dma_c<NMINE>();
+        barrier();               // P
+        if (half) barrier();     // skew: half 1 starts one segment late
+        int kt = 0;
+        for (; kt + 2 < nk; kt += 3) {
+            ktile_w8(kt, L0, L2, o);
+            ktile_w8(kt + 1, L1, L0, o);
+            ktile_w8(kt + 2, L2, L1, o);
+        }
+        if (kt < nk) ktile_w8(kt, L0, L2, o);
+        if (kt + 1 < nk) ktile_w8(kt + 1, L1, L0, o);
+        if (!half) barrier();    // unskew: half 0 waits out half 1's last compute segment
+    };
     auto pipeline = [&](char *L0, char *L1, char *L2, char *L3) __attribute__((always_inline)) {
+        if constexpr (W8) {
+            pipeline_w8(L0, L1, L2);
+            return;
+        }
         // the first DIST tiles (MIDB: one per buffer)
-        issue_tile(kbeg, L0);
-        if constexpr (DIST >= 2) issue_tile(kbeg + BK, L1);
-        if constexpr (DIST >= 3) issue_tile(kbeg + 2 * BK, L2);
-        if constexpr (DIST >= 4) issue_tile(kbeg + 3 * BK, L3);
+        x3_issue(kbeg, L0);
+        if constexpr (DIST >= 2) x3_issue(kbeg + BK, L1);
+        if constexpr (DIST >= 3) x3_issue(kbeg + 2 * BK, L2);
+        if constexpr (DIST >= 4) x3_issue(kbeg + 3 * BK, L3);
         wait_dma_c<(DIST - 1) * NMINE>();
         barrier();
         int kt = 0;
