@@ -12,6 +12,7 @@ _lib = None
 
 c_int = ctypes.c_int
 c_float = ctypes.c_float
+c_double = ctypes.c_double
 c_size_t = ctypes.c_size_t
 c_int64 = ctypes.c_int64
 c_uint32 = ctypes.c_uint32
@@ -146,6 +147,12 @@ _SIGS = {
     "dg_bn_fold": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P]),
     "dg_u8_stage": (c_int, [c_int] * 12 + [_P, _P, _P]),
     "dg_u8_unstage": (c_int, [c_int] * 13 + [_P, _P, _P]),
+    "dg_u8_err_sums": (c_int, [c_int, c_int64, _P, _P, _P, _P]),
+    "dg_err_sums_workspace_size": (c_int, [c_int, c_int64, ctypes.POINTER(c_size_t)]),
+    "dg_f32_err_sums": (c_int, [c_int, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "dg_ssim_workspace_size": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "dg_ssim_u8": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_double, _P, _P, c_size_t, _P]),
+    "dg_ssim_f32": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

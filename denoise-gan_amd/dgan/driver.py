@@ -66,6 +66,24 @@ def sync_before_save(model):
         sync_bn_stats(model)
 
 
+def log_quality(writer, args, gen, y, step):
+    """With `metrics` set in the driver's params: PSNR and SSIM (dgan.metrics, on the device) of the
+    inference output `gen` the image summary already computed against the clean batch `y`, both
+    [-1, 1] read on [0, 1] (scale 0.5, shift 0.5, max_val 1); the batch means go to the summary
+    as Quality/psnr and Quality/ssim.  Reads only: no training state changes."""
+    if not getattr(args, "metrics", 0):
+        return
+    from . import metrics
+    from .models import to_device
+    y = to_device(y, gen.device).contiguous()
+    gen = gen.contiguous()
+    # [-1, 1] on [0, 1]: the error sums scale by 0.5^2, so max_val 2 on the raw values is max_val 1
+    psnr = metrics.psnr(gen, y, max_val=2.0).mean()
+    ssim = metrics.ssim(gen, y, max_val=1.0, scale=0.5, shift=0.5).mean()
+    writer.scalar("Quality/psnr", psnr.item(), step=step)
+    writer.scalar("Quality/ssim", ssim.item(), step=step)
+
+
 def run(args, model, ds, train, save_final=None):
     """The epoch loop of every driver: restore (--retrain), train epochs,
     checkpoint every 5th epoch, final save.  train(model, ds, args, writer)

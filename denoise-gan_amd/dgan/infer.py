@@ -376,6 +376,19 @@ class Denoiser:
             plan.forward(f.tin[t0:t0 + B], f.tout[t0:t0 + B])
         ops.u8_unstage(f.tout[:f.nt], f.u8_out, f.g)
 
+    def run(self, images):
+        """Upload uint8 numpy images [n,h,w,3] (n >= 1) and denoise them on the current stream
+        without reading anything back: the frame whose device buffers `u8_in` / `u8_out` hold the
+        input and the result until the next call on the same shape (dgan/metrics.py Evaluator)."""
+        import torch
+        f = self._frame(*images.shape[:3])
+        f.u8_in.copy_(torch.from_numpy(np.ascontiguousarray(images)))
+        if f.graph is not None:
+            f.graph.replay()
+        else:
+            self._run(f)
+        return f
+
     def denoise(self, images):
         """uint8 [n,h,w,3] or [h,w,3] (numpy or torch) -> the same shape, uint8 numpy."""
         import torch
@@ -387,11 +400,5 @@ class Denoiser:
             a = a[None]
         if a.shape[0] == 0:
             return a.copy()
-        f = self._frame(*a.shape[:3])
-        f.u8_in.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-        if f.graph is not None:
-            f.graph.replay()
-        else:
-            self._run(f)
-        out = f.u8_out.cpu().numpy()
+        out = self.run(a).u8_out.cpu().numpy()
         return out[0] if single else out

@@ -1085,3 +1085,67 @@ def u8_unstage(tiles, out, g):
     call("dg_u8_unstage", n, g.h, g.w, g.Th, g.Tw, g.Sh, g.Sw, g.oy, g.ox, g.gi, g.gj, g.mt, g.ml, _p(tiles), _p(out),
          _stream())
     return out
+
+
+# ---- image quality metrics (include/dgan.h "Image quality metrics") -----------------------------
+def _metric_pair(a, b, what):
+    """A pair of dense uint8 or fp32 device tensors [n,h,w,C] of one shape and dtype."""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float32):
+            raise DGError(f"{what}: expected uint8 or float32 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 4 or not t.is_contiguous():
+            raise DGError(f"{what}: expected dense [n,h,w,C] tensors, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise DGError(f"{what}: expected device tensors (the HIP path has no CPU fallback)")
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise DGError(f"{what}: the images differ: {a.dtype} {tuple(a.shape)} vs {b.dtype} {tuple(b.shape)}")
+    return a.shape
+
+
+def _metric_buf(t, dtype, numel, what):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() != numel:
+        raise DGError(f"{what}: expected a dense {dtype} device tensor of {numel} elements, got {t.dtype} "
+                      f"{tuple(t.shape)}")
+
+
+def err_sums_workspace_bytes(n, count):
+    nb = ctypes.c_size_t()
+    call("dg_err_sums_workspace_size", int(n), int(count), ctypes.byref(nb))
+    return nb.value
+
+
+def err_sums(a, b, sums, ws=None):
+    """sums[n,2] = per image {sum (a-b)^2, sum |a-b|}: exact int64 for uint8 images
+    (dg_u8_err_sums), float64 for fp32 images (dg_f32_err_sums; ws: a uint8 device buffer of
+    err_sums_workspace_bytes)."""
+    n, h, w, C = _metric_pair(a, b, "err_sums")
+    count = h * w * C
+    if a.dtype == torch.uint8:
+        _metric_buf(sums, torch.int64, 2 * n, "err_sums sums")
+        call("dg_u8_err_sums", n, count, _p(a), _p(b), _p(sums), _stream())
+    else:
+        _metric_buf(sums, torch.float64, 2 * n, "err_sums sums")
+        call("dg_f32_err_sums", n, count, _p(a), _p(b), _p(sums), _p(ws), 0 if ws is None else ws.numel(), _stream())
+    return sums
+
+
+def ssim_workspace_bytes(n, h, w, C):
+    nb = ctypes.c_size_t()
+    call("dg_ssim_workspace_size", int(n), int(h), int(w), int(C), ctypes.byref(nb))
+    return nb.value
+
+
+def ssim(a, b, out, ws, max_val, scale=1.0, shift=0.0):
+    """out[n] (float64) = SSIM per image of dense uint8 (dg_ssim_u8) or fp32 (dg_ssim_f32, values
+    read as v * scale + shift) images; ws: a uint8 device buffer of ssim_workspace_bytes."""
+    n, h, w, C = _metric_pair(a, b, "ssim")
+    _metric_buf(out, torch.float64, n, "ssim out")
+    wp, wn = (_p(ws), ws.numel()) if ws is not None else (None, 0)
+    if a.dtype == torch.uint8:
+        if scale != 1.0 or shift != 0.0:
+            raise DGError("ssim: scale / shift apply to fp32 images only")
+        call("dg_ssim_u8", n, h, w, C, _p(a), _p(b), float(max_val), _p(out), wp, wn, _stream())
+    else:
+        call("dg_ssim_f32", n, h, w, C, _p(a), _p(b), float(scale), float(shift), float(max_val), _p(out), wp, wn,
+             _stream())
+    return out

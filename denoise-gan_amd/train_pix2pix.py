@@ -51,6 +51,7 @@ def train(model, dataset, args, writer):
                 gen = model.generator(x, training=False)
                 writer.image("Images/Generated", (255 * (gen.cpu().numpy() + 1) / 2).astype(np.uint8),
                              step=model.epochs + 1)
+                driver.log_quality(writer, args, gen, y, step=model.epochs + 1)
                 writer.flush()
 
 
@@ -94,6 +95,7 @@ params = dict(
     synthetic=0,
     steps_per_epoch=8,   # synthetic pairs only; image_dir runs use images // batch_size
     seed=0,
+    metrics=0,   # 1: log Quality/psnr and Quality/ssim of the inference output at each save_iter
 )
 
 

@@ -612,6 +612,34 @@ int dg_u8_stage(int n, int h, int w, int Th, int Tw, int Sh, int Sw, int oy, int
 int dg_u8_unstage(int n, int h, int w, int Th, int Tw, int Sh, int Sw, int oy, int ox, int gi, int gj, int margin_top,
                   int margin_left, const float *tiles, unsigned char *out, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Image quality metrics (the tf.image.psnr / tf.image.ssim defaults, accumulated in fp64; the
+ * reference has none).  Images are dense device tensors [n][h][w][C], uint8 or fp32, of any byte
+ * alignment.  Results are per image.  No floating-point atomics: a result depends on the shapes
+ * only, never on the order blocks ran in.
+ * ---------------------------------------------------------------------- */
+/* sums[m] = {sum (a - b)^2, sum |a - b|} over image m's `count` bytes, exact 64-bit integers
+ * (count < 2^46).  The entry zeroes sums itself (on `stream`). */
+int dg_u8_err_sums(int n, int64_t count, const unsigned char *a, const unsigned char *b, uint64_t *sums,
+                   dg_stream_t stream);
+/* The same two sums of fp32 images as doubles, differences formed in fp64: block partials in
+ * the workspace, summed in a fixed order. */
+int dg_err_sums_workspace_size(int n, int64_t count, size_t *bytes);
+int dg_f32_err_sums(int n, int64_t count, const float *a, const float *b, double *sums, void *ws, size_t ws_bytes,
+                    dg_stream_t stream);
+/* SSIM (Wang et al. 2004) per image: 11x11 Gaussian window (sigma 1.5, fp64 weights
+ * g[i] = exp(-(i-5)^2 / 4.5) / sum g, applied as a row pass then a column pass), VALID positions
+ * only ((h-10) x (w-10) per channel), c1 = (0.01 max_val)^2, c2 = (0.03 max_val)^2;
+ *   l  = (2 mu_a mu_b + c1) / (mu_a^2 + mu_b^2 + c1),
+ *   cs = (2 (G*ab - mu_a mu_b) + c2) / ((G*a^2 + G*b^2) - (mu_a^2 + mu_b^2) + c2),
+ * out[m] = mean of l * cs over the map and the channels.  h, w >= 11.  dg_ssim_f32 reads every
+ * value as (double)v * scale + shift.  The workspace holds one partial per block. */
+int dg_ssim_workspace_size(int n, int h, int w, int C, size_t *bytes);
+int dg_ssim_u8(int n, int h, int w, int C, const unsigned char *a, const unsigned char *b, double max_val,
+               double *out, void *ws, size_t ws_bytes, dg_stream_t stream);
+int dg_ssim_f32(int n, int h, int w, int C, const float *a, const float *b, double scale, double shift,
+                double max_val, double *out, void *ws, size_t ws_bytes, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
