@@ -238,7 +238,38 @@ class GraphPlan:
         self.param_grads = param_grads
         nodes = graph.nodes
         cons = graph.consumers()
-        # ---- shape inference + descriptors ----
+        conv_nodes = [n for n in nodes[1:] if n.kind == "conv"]
+        # The planning passes, in the order their inputs require:
+        #   * shapes and descriptors come first: every later pass reads self.shape / self.desc;
+        #   * concat membership (slice_of) before premask and BN + Add, which exclude concat slices,
+        #     and before the buffers, where a member is a view of its concat's buffer;
+        #   * premask and BN + Add before the buffers: the gradient schedule shares the fused BN's
+        #     gradient with its Add's (_alias_add_grads);
+        #   * the planes before everything that feeds them; the conv -> conv and pool feeds read
+        #     premask and add x / dy buffers and fwd_out / bwd_out links to cplanes;
+        #   * the fp16 producer copies need those x / dy buffers as the feeds left them;
+        #   * the fused pools before planes-only (a conv with a fused pool keeps no planes-only
+        #     output), which also reads the feeds' fwd_out;
+        #   * the fp16x3 gradient scales edit fed_dy / pool_gout, which the feed pass created, and
+        #     read fused_pool; the fp16x3 activation scales read fwd_out / pool_out and fused_conv;
+        #   * the workspace needs only shapes and descriptors.
+        self._infer_shapes(H, W, math)
+        self._plan_concats(nodes, cons)
+        self._plan_premask(nodes, cons)
+        self._plan_bn_add(nodes, cons)
+        self._alloc_buffers(nodes, cons, slots, alias)
+        self._plan_planes(conv_nodes, slots, alias)
+        self._plan_feeds(nodes, cons, conv_nodes, slots)
+        self._plan_f16_copies(cons, conv_nodes, slots)
+        self._plan_fused_pools(nodes, cons, slots, alias)
+        self._plan_planes_only(cons, conv_nodes, slots, alias)
+        self._plan_grad_scales(cons, conv_nodes, slots)
+        self._plan_act_scales(nodes, cons, conv_nodes, slots, alias)
+        self._plan_workspace(nodes)
+
+    def _infer_shapes(self, H, W, math):
+        """Shape inference and the conv descriptors."""
+        graph, N, nodes = self.g, self.N, self.g.nodes
         shp = {}
         self.desc = {}
         shp[graph.input.id] = (N, H, W, graph.input.C)
@@ -271,11 +302,15 @@ class GraphPlan:
                 shp[n.out.id] = x
         self.shape = shp
         self.out_shape = shp[graph.output.id]
-        # ---- zero-copy concat membership ----
-        # member t of concat node c becomes a channel slice of c's buffer when t is
-        # produced by a node (not the graph input), belongs to one concat only, and
-        # every other consumer of t precedes c's consumers (their gradient
-        # contributions then accumulate after c's consumer has written the slice).
+
+    def _plan_concats(self, nodes, cons):
+        """Zero-copy concat membership.
+
+        Member t of concat node c becomes a channel slice of c's buffer when t is
+        produced by a node (not the graph input), belongs to one concat only, and
+        every other consumer of t precedes c's consumers (their gradient
+        contributions then accumulate after c's consumer has written the slice)."""
+        graph = self.g
         self.slice_of = {}   # tensor id -> (concat tensor id, channel offset)
         for n in nodes:
             if n.kind != "concat":
@@ -288,11 +323,15 @@ class GraphPlan:
                 if ok:
                     self.slice_of[t.id] = (n.out.id, off)
                 off += t.C
-        # ---- fused activation gradients ----
-        # a conv whose activation output feeds exactly one consumer that can fold
-        # act'(z) into the gradient it writes (a conv's masked bwd_data epilogue, a
-        # max-pool's routing pass, or -- for ReLU -- the nearest-upsample+ReLU
-        # backward, whose x > 0 mask is the same) skips its own act_bwd pass.
+
+    def _plan_premask(self, nodes, cons):
+        """Fused activation gradients.
+
+        A conv whose activation output feeds exactly one consumer that can fold
+        act'(z) into the gradient it writes (a conv's masked bwd_data epilogue, a
+        max-pool's routing pass, or -- for ReLU -- the nearest-upsample+ReLU
+        backward, whose x > 0 mask is the same) skips its own act_bwd pass."""
+        graph = self.g
         self.premask = set()
         for n in nodes[1:]:
             if n.kind != "conv" or ops.act_id(n.attrs["act"]) == 0 or n.out.id == graph.output.id:
@@ -303,11 +342,15 @@ class GraphPlan:
             c = cs[0]
             if c.kind in ("conv", "maxpool") or (c.kind == "upsample" and ops.act_id(n.attrs["act"]) == 2):
                 self.premask.add(n.out.id)
-        # ---- BatchNorm + residual Add ----
-        # a linear BN whose only consumer is an Add (the SR residual blocks, srgan.py:165 /
-        # :180, fsrgan.py:176 / :214) writes act(BN(y)) + skip straight into the Add's output
-        # in a training forward; backward, the BN reads the Add's output gradient (aliased:
-        # the Add passes it through unchanged) and the Add only routes it to the skip input
+
+    def _plan_bn_add(self, nodes, cons):
+        """BatchNorm + residual Add.
+
+        A linear BN whose only consumer is an Add (the SR residual blocks, srgan.py:165 /
+        :180, fsrgan.py:176 / :214) writes act(BN(y)) + skip straight into the Add's output
+        in a training forward; backward, the BN reads the Add's output gradient (aliased:
+        the Add passes it through unchanged) and the Add only routes it to the skip input."""
+        graph, train = self.g, self.train
         self.bn_add = {}   # bn node idx -> (add node, skip input tensor)
         for a in (nodes[1:] if train and not os.environ.get("DG_NO_BN_ADD") else []):
             if a.kind != "add" or a.out.id in self.slice_of or a.out.id == graph.output.id:
@@ -322,7 +365,11 @@ class GraphPlan:
                     self.bn_add[b.idx] = (a, o)
                     break
         self.add_of_bn = {a.idx: nodes[b] for b, (a, _) in self.bn_add.items()}   # add idx -> its BN
-        # ---- activation buffers per slot ----
+
+    def _alloc_buffers(self, nodes, cons, slots, alias):
+        """Activation buffers per slot, and (training) the gradient buffers shared by the slots
+        with their beta schedule."""
+        graph, N, shp, device, train = self.g, self.N, self.shape, self.device, self.train
         self.slots = []
         for k in range(slots):
             if alias is not None and k == 0:
@@ -336,7 +383,6 @@ class GraphPlan:
                 if n.kind == "bn":
                     s[n.name] = (torch.empty(n.out.C, device=device), torch.empty(n.out.C, device=device))
             self.saved.append(s)
-        # ---- gradient buffers (shared by slots) + beta schedule ----
         if train:
             self.grad = self._alloc_set(nodes, shp)
             self._schedule(nodes, cons)
@@ -347,25 +393,28 @@ class GraphPlan:
                     s0 = shp[n.out.id]
                     mx = max(mx, int(np.prod(s0[:3])) * _ld(s0[3]))
             self.scratch = torch.empty(max(mx, 4), dtype=torch.float32, device=device)
-        # ---- bf16x6 operand planes shared between the ops of a conv ----
-        # w: one buffer per conv of the NETWORK and weight-plane layout
-        # (arena.wplanes[(layer, format, bytes)]), shared by all its plans of that
-        # layout (e.g. the VGG19 forward over 2N images and the backward over N);
-        # plans whose GEMMs run another arithmetic (a VGG19 planned at 32^2 on
-        # bf16x6 and at 256^2 on fp16x3) get buffers of their own, each stamped
-        # with the weight version it was split from; x: per slot, split by fwd and
-        # kept for bwd_filter (trainable plans that own their activations); dy: one
-        # scratch per plan.
+
+    def _plan_planes(self, conv_nodes, slots, alias):
+        """The bf16x6 operand planes shared between the ops of a conv.
+
+        w: one buffer per conv of the NETWORK and weight-plane layout
+        (arena.wplanes[(layer, format, bytes)]), shared by all its plans of that
+        layout (e.g. the VGG19 forward over 2N images and the backward over N);
+        plans whose GEMMs run another arithmetic (a VGG19 planned at 32^2 on
+        bf16x6 and at 256^2 on fp16x3) get buffers of their own, each stamped
+        with the weight version it was split from; x: per slot, split by fwd and
+        kept for bwd_filter (trainable plans that own their activations); dy: one
+        scratch per plan."""
+        arena, device, train = self.arena, self.device, self.train
         wplanes = getattr(arena, "wplanes", None)
         if wplanes is None:
             wplanes = arena.wplanes = {}
-        conv_nodes = [n for n in nodes[1:] if n.kind == "conv"]
         descs = [self.desc[n.idx] for n in conv_nodes]
-        keep_x = train and param_grads and alias is None
+        keep_x = train and self.param_grads and alias is None
         # fp16 weight copies of a trainable network: views into one fp16 shadow of the
         # arena (arena.half), converted by ONE launch per forward (dg_to_f16) instead of
         # one conversion per conv (the weights change with every Adam step)
-        half = (not getattr(arena, "frozen", False) and not os.environ.get("DG_NO_F16_WARENA")
+        half = (not getattr(arena, "frozen", False)
                 and any(d.math == ops.MATH_FP16 and (d.plane_mask[0] | d.plane_mask[1]) & ops.TENSOR_W
                         for d in descs))
         if half and getattr(arena, "half", None) is None:
@@ -400,20 +449,24 @@ class GraphPlan:
                 for p, p0 in zip(ps, self.cplanes[0].values()):
                     p.dy = p0.dy   # one dy scratch per plan
             self.cplanes.append({n.idx: p for n, p in zip(conv_nodes, ps)})
-        # producer-written planes on conv -> conv chains (VGG19): a conv whose
-        # activation output feeds exactly one conv (premask) writes that
-        # consumer's x planes in its forward epilogue, and the consumer's
-        # input-gradient epilogue writes the producer's dy planes -- no split
-        # pass for either tensor.  Every fed tensor has a buffer of its own.
+
+    def _plan_feeds(self, nodes, cons, conv_nodes, slots):
+        """The conv -> conv and pool feeds.
+
+        Producer-written planes on conv -> conv chains (VGG19): a conv whose
+        activation output feeds exactly one conv (premask) writes that
+        consumer's x planes in its forward epilogue, and the consumer's
+        input-gradient epilogue writes the producer's dy planes -- no split
+        pass for either tensor.  Every fed tensor has a buffer of its own."""
+        device, train = self.device, self.train
         self.fed_x, self.fed_dy = set(), set()
         self.pool_out = [dict() for _ in range(slots)]    # maxpool node -> consumer conv's x planes
         self.pool_gout = [dict() for _ in range(slots)]   # maxpool node -> producer conv's dy planes
-        feed = not os.environ.get("DG_NO_FEED")
         # (producer-written planes are bf16x6 or, for a consumer whose forward runs fp16x3,
         # fp16x3 planes -- the PlaneBuf's fmt tells the producer; an fp16 descriptor's
         # planes are the fp16 copies its own ops convert, so neither end of a feed may be fp16)
         x6 = lambda d: d.math in (ops.MATH_BF16X6, ops.MATH_F16X3)   # noqa: E731
-        for m in (nodes[1:] if feed else []):
+        for m in nodes[1:]:
             # max pool between two convs: its output is the next conv's input,
             # its input gradient the previous conv's dy (premask: act' folded in)
             if m.kind != "maxpool" or m.out.C % 16:
@@ -439,7 +492,7 @@ class GraphPlan:
                         pn.dy = ops.PlaneBuf(dn.plane_bytes(ops.TENSOR_DY), device, dn.plane_format(ops.TENSOR_DY))
                         self.pool_gout[k][m.idx] = pn.dy
                     self.fed_dy.add(n.idx)
-        for n in (conv_nodes if feed else []):
+        for n in conv_nodes:
             t = n.out
             if t.id not in self.premask or cons[t.id][0].kind != "conv":
                 continue
@@ -460,15 +513,19 @@ class GraphPlan:
                     pn.dy = ops.PlaneBuf(dn.plane_bytes(ops.TENSOR_DY), device, dn.plane_format(ops.TENSOR_DY))
                     self.cplanes[k][c.idx].bwd_out = pn.dy
                 self.fed_dy.add(n.idx)
-        # ---- fp16 operand copies written by their producers (mixed_float16) ----
-        # an fp16 conv reads fp16 copies of x and dy (its dg_conv_planes_t buffers, converted
-        # per call otherwise): the BN / PReLU / Add producing its input writes the x copy beside
-        # its fp32 output, and the BN / PReLU right after it, whose backward produces its output
-        # gradient, writes the dy copy -- no conversion launch before the GEMMs
+
+    def _plan_f16_copies(self, cons, conv_nodes, slots):
+        """The fp16 operand copies written by their producers (mixed_float16).
+
+        An fp16 conv reads fp16 copies of x and dy (its dg_conv_planes_t buffers, converted
+        per call otherwise): the BN / PReLU / Add producing its input writes the x copy beside
+        its fp32 output, and the BN / PReLU right after it, whose backward produces its output
+        gradient, writes the dy copy -- no conversion launch before the GEMMs."""
+        train = self.train
         self.h_x_out = {}    # producer node idx -> consuming conv node idx
         self.h_dy_out = {}   # node idx -> the conv node whose dy its backward writes
         f16 = lambda d: d.math == ops.MATH_FP16   # noqa: E731
-        for c in (conv_nodes if (train and feed and not os.environ.get("DG_NO_F16_FEED")) else []):
+        for c in (conv_nodes if train else []):
             dc = self.desc[c.idx]
             if not f16(dc):
                 continue
@@ -484,17 +541,21 @@ class GraphPlan:
                     and (dc.plane_mask[ops.OP_BWD_DATA] | dc.plane_mask[ops.OP_BWD_FILTER]) & ops.TENSOR_DY
                     and self.cplanes[0][c.idx].dy is not None):
                 self.h_dy_out[cs[0].idx] = c.idx
-        # ---- max pools fused into their conv's forward epilogue ----
-        # a conv (ReLU / LeakyReLU / linear) whose output feeds only a 2x2 max
-        # pool, on a plan that can run the pool in its epilogue, writes the
-        # pooled values, their planes and a {argmax, sign} byte per pooled
-        # element instead of its full-size activation; the pool's backward
-        # routes from those bytes.  An aliasing plan follows its forward plan.
+
+    def _plan_fused_pools(self, nodes, cons, slots, alias):
+        """Max pools fused into their conv's forward epilogue.
+
+        A conv (ReLU / LeakyReLU / linear) whose output feeds only a 2x2 max
+        pool, on a plan that can run the pool in its epilogue, writes the
+        pooled values, their planes and a {argmax, sign} byte per pooled
+        element instead of its full-size activation; the pool's backward
+        routes from those bytes.  An aliasing plan follows its forward plan."""
+        graph, N, shp, device = self.g, self.N, self.shape, self.device
         self.fused_pool = {}   # maxpool node idx -> producing conv node
         self.pool_idx = [dict() for _ in range(slots)]
         if alias is not None:
             self.fused_pool = dict(alias.fused_pool)
-        elif not os.environ.get("DG_NO_FUSED_POOL"):
+        else:
             for m in nodes[1:]:
                 if m.kind != "maxpool":
                     continue
@@ -512,13 +573,17 @@ class GraphPlan:
                     self.pool_idx[k][midx] = alias.pool_idx[0][midx][:N]
                 else:
                     self.pool_idx[k][midx] = torch.empty(shp[nodes[midx].out.id], dtype=torch.uint8, device=device)
-        # ---- planes-only activations ----
-        # in a plan without parameter gradients (the frozen VGG19), a conv whose
-        # activation output feeds exactly one conv as producer-written planes
-        # skips its fp32 output: the consumer's forward reads the planes, and its
-        # masked input gradient takes act' from the planes' sign
-        # (dg_conv_bwd_data_xmask).  An aliasing plan reads its forward plan's
-        # planes (the first N images' rows).
+
+    def _plan_planes_only(self, cons, conv_nodes, slots, alias):
+        """Planes-only activations.
+
+        In a plan without parameter gradients (the frozen VGG19), a conv whose
+        activation output feeds exactly one conv as producer-written planes
+        skips its fp32 output: the consumer's forward reads the planes, and its
+        masked input gradient takes act' from the planes' sign
+        (dg_conv_bwd_data_xmask).  An aliasing plan reads its forward plan's
+        planes (the first N images' rows)."""
+        graph = self.g
         self.nofp32 = set()
         if alias is not None:
             self.nofp32 = set(alias.nofp32)
@@ -528,7 +593,7 @@ class GraphPlan:
                 c = cons[n.out.id][0]
                 src = alias.cplanes[0][c.idx].x
                 self.cplanes[0][c.idx].x = src.view(self.desc[c.idx].plane_bytes(ops.TENSOR_X))
-        elif not param_grads and feed and not os.environ.get("DG_NO_PLANES_ONLY"):
+        elif not self.param_grads:
             for n in conv_nodes:
                 t = n.out
                 if (n.idx in self.fused_conv or t.id == graph.output.id or t.id not in self.premask
@@ -537,14 +602,18 @@ class GraphPlan:
                 c = cons[t.id][0]
                 if c.kind == "conv" and all(self.cplanes[k][n.idx].fwd_out is not None for k in range(slots)):
                     self.nofp32.add(n.idx)
-        # ---- fp16x3 input gradients (DG_MATH_F16X3: VGG19's backward) ----
-        # a gradient has no static range: each fp16x3 dy is scaled from a bound of its max
-        # (include/dgan.h dg_conv_set_grad_scale).  Per conv a device max slot gmax (max |dy|
-        # of that conv, written by atomicMax by the op that produces it) and a weight bound
-        # gwb (max_ci sum |w|, recomputed when the frozen weights change).  A conv's dy planes
-        # written by its consumer conv c are scaled from (gmax[c], gwb[c]) (|dy| <= that
-        # product); written by a pool's backward or split from the fp32 graph-output gradient,
-        # from their measured max gmax[itself].
+
+    def _plan_grad_scales(self, cons, conv_nodes, slots):
+        """The fp16x3 input gradients' scales (DG_MATH_F16X3: VGG19's backward).
+
+        A gradient has no static range: each fp16x3 dy is scaled from a bound of its max
+        (include/dgan.h dg_conv_set_grad_scale).  Per conv a device max slot gmax (max |dy|
+        of that conv, written by atomicMax by the op that produces it) and a weight bound
+        gwb (max_ci sum |w|, recomputed when the frozen weights change).  A conv's dy planes
+        written by its consumer conv c are scaled from (gmax[c], gwb[c]) (|dy| <= that
+        product); written by a pool's backward or split from the fp32 graph-output gradient,
+        from their measured max gmax[itself]."""
+        graph, device, train = self.g, self.device, self.train
         self.x3_top = None
         self.x3_measure_dy = set()   # convs whose fp32 dy is measured (absmax) before their backward ops
         x3g = [n for n in conv_nodes if train and self.desc[n.idx].plane_format(ops.TENSOR_DY) == ops.PLANES_F16X3]
@@ -590,20 +659,24 @@ class GraphPlan:
                 p = producer_conv(n.ins[0])
                 d.set_grad_scale(dy_m=src[0], dy_g=src[1], dx_m=gm(n), dx_g=gw(n),
                                  dx_max=gm(p) if p is not None else None)
-        # ---- fp16x3 activation scales (include/dgan.h dg_conv_set_act_scale) ----
-        # a conv's fp16x3 x planes carry the scale their producer wrote them with.  A conv that
-        # writes its consumer's planes -- in its epilogue, its fused pool's, or through an unfused
-        # pool -- scales them from its output bound: (max |its input|, measured) x (max over output
-        # channels of sum |w|) + max |bias| (awb, per weight version), and measures max |its
-        # output| (the consumer's input) in the same epilogue.  Every other fp16x3 x operand is
-        # measured by the op that splits it (a plain max slot).  VGG19's activations (a
-        # preprocessed image of +-128 onwards) thus keep 22 bits down to 2^-17 of each bound.
-        # The measured maxima are per slot (amax[slot]): a slot's forward re-measures them, and its
-        # kept x planes must be read back (bwd_filter) with the scale of the slot that wrote them --
-        # D(real) and D(fake) of the SR discriminator are two slots of one plan whose inputs may
-        # sit in different binades.  The descriptors are shared by the slots, so each slot's scale
-        # context is set on them before that slot's forward and backward (_use_act_slot; host-side
-        # pointers, baked into the launches).
+
+    def _plan_act_scales(self, nodes, cons, conv_nodes, slots, alias):
+        """The fp16x3 activation scales (include/dgan.h dg_conv_set_act_scale).
+
+        A conv's fp16x3 x planes carry the scale their producer wrote them with.  A conv that
+        writes its consumer's planes -- in its epilogue, its fused pool's, or through an unfused
+        pool -- scales them from its output bound: (max |its input|, measured) x (max over output
+        channels of sum |w|) + max |bias| (awb, per weight version), and measures max |its
+        output| (the consumer's input) in the same epilogue.  Every other fp16x3 x operand is
+        measured by the op that splits it (a plain max slot).  VGG19's activations (a
+        preprocessed image of +-128 onwards) thus keep 22 bits down to 2^-17 of each bound.
+        The measured maxima are per slot (amax[slot]): a slot's forward re-measures them, and its
+        kept x planes must be read back (bwd_filter) with the scale of the slot that wrote them --
+        D(real) and D(fake) of the SR discriminator are two slots of one plan whose inputs may
+        sit in different binades.  The descriptors are shared by the slots, so each slot's scale
+        context is set on them before that slot's forward and backward (_use_act_slot; host-side
+        pointers, baked into the launches)."""
+        device = self.device
         self.act_feeds = {}      # producer conv idx -> (consumer conv node, unfused pool node or None)
         self.act_measure = []    # convs whose input max is measured before them (input not a conv's output)
         self.pool_scale = [dict() for _ in range(slots)]   # unfused maxpool idx -> its planes' scale source
@@ -661,7 +734,10 @@ class GraphPlan:
                                       if x is not None or y is not None or ymax is not None])
             self._act_ci = ci
             self._use_act_slot(0)
-        # ---- workspace ----
+
+    def _plan_workspace(self, nodes):
+        """The workspace size: the largest any node's ops ask for."""
+        shp = self.shape
         ws = [0]
         for n in nodes[1:]:
             sx = shp[n.ins[0].id]

@@ -29,18 +29,6 @@ ALPHA = 0.3       # Keras LeakyReLU default (pix2pix.py:121, :213)
 BN_EPS = 1e-3     # Keras BatchNormalization defaults (pix2pix.py:119)
 BN_MOMENTUM = 0.99
 DROP_RATE = 0.5   # pix2pix.py:138
-FEED_DY = not os.environ.get("DG_NO_FEED_DY")  # BN backward writes the conv's dy planes
-FEED_X = not os.environ.get("DG_NO_FEED_X")    # BN forward writes the next convs' x planes
-DY_PLANES_ONLY = not os.environ.get("DG_DY_FP32")  # ... and then skips the fp32 dy (its readers take the planes)
-# fp16x3 activation planes scaled from their producers' bounds (ActBounds); DG_NO_ACT_BOUND: the
-# round-4 static 2^-4 (same-box A/B only: |x| < 2 then loses bits)
-ACT_BOUNDS = not os.environ.get("DG_NO_ACT_BOUND")
-# BN backward of the blocks without dropout takes act'(z) from y and the forward's scale / shift
-# (dg_bn_bwd_seg_r) instead of reading z; DG_BN_READ_Z: read z (same-box A/B)
-BN_RZ = not os.environ.get("DG_BN_READ_Z")
-# D's input gradient into a LeakyReLU block without BN masked in the conv epilogue; DG_NO_MASK_DZ:
-# a separate act_bwd pass (same-box A/B)
-MASK_DZ = not os.environ.get("DG_NO_MASK_DZ")
 
 
 def _eb(buf):
@@ -83,7 +71,7 @@ def grad_bounds(descs, planes, device):
     out = []
     for d, P in zip(descs, planes):
         b = None
-        if FEED_DY and P is not None and P.dy is not None and P.dy.fmt == ops.PLANES_F16X3:
+        if P is not None and P.dy is not None and P.dy.fmt == ops.PLANES_F16X3:
             b = ops.max_slot(device=device)
             d.set_grad_scale(dy_m=b)
         out.append(b)
@@ -269,10 +257,92 @@ def _empty(shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
+class _BlockPlan:
+    """What the two pix2pix plans share.  Both are chains of conv blocks run once over `halves`
+    independent image sets of N images, block 0 a conv + LeakyReLU and the inner blocks conv + BN
+    + activation with BatchNorm per half; the subclass sets arena, bn, N, halves and the saved
+    statistics mean / inv (name -> [half, channel])."""
+
+    def _wire_planes(self, descs, device, train):
+        """planes, gbound and ab of the chain `descs`.  Training: the bf16x6 / fp16x3 operand
+        planes shared by the ops of each layer (x: fwd -> bwd_filter, w: fwd -> bwd_data, dy:
+        bwd_filter -> bwd_data), block 0 writing block 1's x planes in its epilogue; one dy bound
+        per conv whose dy planes are fp16x3 (grad_bounds); and the fp16x3 x planes scaled from
+        their producers' bounds (ActBounds): block 1's from (max |input|, block 0's weight bound),
+        block k's from zb[k-1], the bound of the BN output it reads."""
+        self.planes, self.gbound, self.ab = [None] * len(descs), [None] * len(descs), None
+        if not train:
+            return
+        self.planes = ops.plan_planes(descs, device)
+        if self.planes[1].x is not None:
+            self.planes[0].fwd_out = self.planes[1].x
+        self.gbound = grad_bounds(descs, self.planes, device)
+        if any(x3_planes(P) for P in self.planes):
+            self.ab = ActBounds(len(descs), device)
+            for k, d in enumerate(descs):
+                if x3_planes(self.planes[k]):
+                    d.set_act_scale(x=self.ab.first_src if k == 1 else self.ab.zb[k - 1])
+            if x3_planes(self.planes[1]):
+                descs[0].set_act_scale(y=self.ab.first_src)
+
+    def _half(self, t, h):
+        return t[h * self.N:(h + 1) * self.N]
+
+    def _fwd_planes(self):
+        """The layer planes with x and w invalidated (a forward re-splits both)."""
+        for p in self.planes:
+            if p is not None:
+                p.invalidate(ops.TENSOR_X | ops.TENSOR_W)
+        return self.planes
+
+    def _bn_fwd(self, name, y, z, act, training, ws, outs=(), drop_rate=0.0, seed_of=None, step_dev=None,
+                z_bound=None, copy=None):
+        """outs: (plane index k, its x channel count, column) -- the BN output is also written
+        into plane k's kept x planes at that column (training), which the column-0 write
+        completes.  Training: one segmented call, each half normalised by its own statistics and
+        the moving averages updated half 0 then half 1 (the reference's two separate calls);
+        dropout seeds follow seed_of(half)."""
+        A = self.arena
+        if training:
+            rows = z[..., 0].numel()
+            zp = [zplanes(self.planes[k].x, rows, pc, col) for k, pc, col in outs]
+            seed0 = seed_of(0) if seed_of else 0
+            stride = ((seed_of(1) - seed0) & 0xFFFFFFFF) if (seed_of and self.halves > 1) else 0
+            ops.bn_fwd_train(y, A.param(f"{name}/gamma"), A.param(f"{name}/beta"), self.mean[name], self.inv[name],
+                             self.bn.mean[name], self.bn.var[name], z, act=act, alpha=ALPHA, momentum=BN_MOMENTUM,
+                             eps=BN_EPS, drop_rate=drop_rate, drop_seed=seed0, step_dev=step_dev, ws=ws, z_planes=zp,
+                             segments=self.halves, drop_seed_stride=stride, z_bound=z_bound, copy=copy)
+            for k, _, col in outs:
+                if col == 0:
+                    self.planes[k]._filled(ops.TENSOR_X)
+            return
+        for hv in range(self.halves):
+            ops.bn_fwd_infer(self._half(y, hv), A.param(f"{name}/gamma"), A.param(f"{name}/beta"), self.bn.mean[name],
+                             self.bn.var[name], self._half(z, hv), act=act, alpha=ALPHA, eps=BN_EPS)
+
+    def _bn_bwd(self, name, dz, z, y, dy, act, beta, ws, P, mean, inv, dgamma, dbeta, segments, dy_bound,
+                drop_rate=0.0):
+        """BN backward over `segments` halves with their statistics mean / inv; dgamma / dbeta
+        (None: no parameter gradients) sum over the halves.  act'(z) comes from y and the
+        forward's scale / shift (dg_bn_bwd_seg_r); only a dropout block reads z.
+        P: the consuming conv's ConvPlanes -- when it keeps dy planes, the BN backward writes
+        them instead of the fp32 dy (no split pass before the conv's backward GEMMs, whose ops
+        read the planes; fp16x3 planes with their bound into dy_bound, the conv's scale source)
+        and marks them ready."""
+        A = self.arena
+        feed = P is not None and P.dy is not None
+        ops.bn_bwd(dz, z, y, A.param(f"{name}/gamma"), mean, inv, dy, dgamma, dbeta, act=act, alpha=ALPHA,
+                   drop_rate=drop_rate, beta=beta, ws=ws, dy_planes=plane_rows(P.dy, dy, 0) if feed else None,
+                   segments=segments, dy_fp32=not feed, dy_bound=dy_bound if feed else None,
+                   offset=A.param(f"{name}/beta"))
+        if feed:
+            P._filled(ops.TENSOR_DY)
+
+
 # ---------------------------------------------------------------------------
 # U-Net generator plan (pix2pix.py:144-192)
 # ---------------------------------------------------------------------------
-class GeneratorPlan:
+class GeneratorPlan(_BlockPlan):
     """Static forward/backward schedule of the U-Net for one input shape.
 
     halves: independent images sets batched into ONE pass (half 0 = G(x),
@@ -332,34 +402,17 @@ class GeneratorPlan:
         s["x"] = None
         s["out"] = None
         self.s = s
+        self.mean, self.inv = s["mean"], s["inv"]
         # gradient buffers
         if train:
             self.dcat = [torch.empty_like(c) for c in s["cat"]]
             self.dz8 = torch.empty_like(s["z8"])
             maxdy = max([d.N * d.Ho * d.Wo * d.Cout for d in self.ddesc + self.udesc + [self.ldesc]])
             self.dy = _empty((maxdy,), device)
-        # bf16x6 operand planes shared by the ops of each layer (x: fwd ->
-        # bwd_filter, w: fwd -> bwd_data, dy: bwd_filter -> bwd_data)
-        descs = self.ddesc + self.udesc + [self.ldesc]
-        self.planes = ops.plan_planes(descs, device) if train else [None] * len(descs)
-        # down1 (conv + LeakyReLU, no BN) writes down2's x planes in its epilogue
-        if train and FEED_X and self.planes[1].x is not None:
-            self.planes[0].fwd_out = self.planes[1].x
-        self.gbound = grad_bounds(descs, self.planes, device) if train else [None] * len(descs)
-        # fp16x3 activation planes scaled from their producers' bounds (ActBounds): down l's BN
-        # output -> zb[l] (down l+1's x), up u's BN output with the skip half of its concat ->
-        # zb[8+u] (up u+1's x), down1's conv output -> (max |x|, down1's weight bound) (down2's x)
-        self.ab = None
-        if train and ACT_BOUNDS and any(x3_planes(P) for P in self.planes):
-            self.ab = ActBounds(16, device)
-            for k, d in enumerate(descs):
-                if not x3_planes(self.planes[k]):
-                    continue
-                # (plane index k: 0-7 down1-down8, 8-14 up1-up7, 15 last; the x of k >= 2 is the BN
-                # output of block k-1, zb[k-1])
-                d.set_act_scale(x=self.ab.first_src if k == 1 else self.ab.zb[k - 1])
-            if x3_planes(self.planes[1]) and FEED_X:
-                self.ddesc[0].set_act_scale(y=self.ab.first_src)
+        # operand planes and their scale sources (plane index k: 0-7 down1-down8, 8-14 up1-up7, 15
+        # last): down l's BN output -> zb[l] (down l+1's x), up u's BN output with the skip half of
+        # its concat -> zb[8+u] (up u+1's x), down1's conv output -> (max |x|, down1's weight bound)
+        self._wire_planes(self.ddesc + self.udesc + [self.ldesc], device, train)
         self.ws_bytes = max([d.max_ws() for d in self.ddesc + self.udesc + [self.ldesc]] + [self._bn_ws_max()])
 
     @property
@@ -371,9 +424,6 @@ class GeneratorPlan:
         for d in self.ddesc + self.udesc:
             m = max(m, ops.bn_workspace_bytes(self.N * d.Ho * d.Wo, d.Cout, self.halves))
         return m
-
-    def _half(self, t, h):
-        return t[h * self.N:(h + 1) * self.N]
 
     # views ---------------------------------------------------------------
     def z_view(self, s, l):
@@ -400,10 +450,9 @@ class GeneratorPlan:
         s["x"], s["out"] = x, out
         A = self.arena
         P = self._fwd_planes()
-        feed = FEED_X and training
 
         def xplanes(k):  # plane index k's kept x planes (None: its ops split x themselves)
-            return P[k].x if feed and P[k] is not None else None
+            return P[k].x if training and P[k] is not None else None
 
         ab = self.ab
         if ab is not None:
@@ -428,10 +477,7 @@ class GeneratorPlan:
                 outs = [(nxt, co, 0)] if xplanes(nxt) is not None else []
                 if 1 <= l <= 6 and xplanes(15 - l) is not None and not (ab is not None and x3_planes(P[15 - l])):
                     outs.append((15 - l, self.ups[7 - l][1], self.ups[6 - l][2]))
-                self._bn_fwd(s, name, y, z, "lrelu", training, ws, outs=outs,
-                             z_bound=ab.zb[l] if ab is not None else None)
-                if xplanes(nxt) is not None:
-                    P[nxt]._filled(ops.TENSOR_X)
+                self._bn_fwd(name, y, z, "lrelu", training, ws, outs, z_bound=ab.zb[l] if ab is not None else None)
             h = z
         for u, (name, ci, co, drop) in enumerate(self.ups):
             d = self.udesc[u]
@@ -449,20 +495,11 @@ class GeneratorPlan:
                 outs.append((k, self.ups[u + 1][1], 0))
                 if ab is not None and x3_planes(P[k]):   # (+ the skip half, down 6-u's output, under one bound)
                     copy = (self.z_view(s, 6 - u), co, ab.zb[6 - u])
-            self._bn_fwd(s, name, y, z, "relu", training, ws, rate, lambda hv: dropout_seed(drop_seed, u, hv),
-                         step_dev, outs=outs, z_bound=ab.zb[8 + u] if ab is not None else None, copy=copy)
-            if outs:
-                P[k]._filled(ops.TENSOR_X)
+            self._bn_fwd(name, y, z, "relu", training, ws, outs, rate, lambda hv: dropout_seed(drop_seed, u, hv),
+                         step_dev, z_bound=ab.zb[8 + u] if ab is not None else None, copy=copy)
             h = s["cat"][u]
         self.ldesc.fwd(h, A.param("last/kernel"), out, bias=A.param("last/bias"), act="tanh", ws=ws, planes=P[15])
         return out
-
-    def _fwd_planes(self):
-        """The layer planes with x and w invalidated (a forward re-splits both)."""
-        for p in self.planes:
-            if p is not None:
-                p.invalidate(ops.TENSOR_X | ops.TENSOR_W)
-        return self.planes
 
     def _bwd_planes(self, i):
         p = self.planes[i]
@@ -470,43 +507,11 @@ class GeneratorPlan:
             p.invalidate(ops.TENSOR_DY)
         return p
 
-    def _bn_fwd(self, s, name, y, z, act, training, ws, drop_rate=0.0, seed_of=None, step_dev=None, outs=(),
-                z_bound=None, copy=None):
-        """outs: (plane index k, its x channel count, column) -- the BN output is
-        also written into plane k's kept x planes at that column (training).
-        Training: one segmented call, each half normalised by its own statistics
-        and the moving averages updated half 0 then half 1 (the reference's
-        two generator calls); dropout seeds follow dropout_seed(base, layer, half)."""
+    def _bn_bwd_block(self, k, name, dz, z, y, dy, act, beta, ws, P, drop_rate=0.0):
+        """The BN backward of block `name` (plane index k) over all halves, with parameter gradients."""
         A = self.arena
-        if training:
-            rows = z[..., 0].numel()
-            zp = [zplanes(self.planes[k].x, rows, pc, col) for k, pc, col in outs]
-            seed0 = seed_of(0) if seed_of else 0
-            stride = ((seed_of(1) - seed0) & 0xFFFFFFFF) if (seed_of and self.halves > 1) else 0
-            ops.bn_fwd_train(y, A.param(f"{name}/gamma"), A.param(f"{name}/beta"), s["mean"][name], s["inv"][name],
-                             self.bn.mean[name], self.bn.var[name], z, act=act, alpha=ALPHA, momentum=BN_MOMENTUM,
-                             eps=BN_EPS, drop_rate=drop_rate, drop_seed=seed0, step_dev=step_dev, ws=ws, z_planes=zp,
-                             segments=self.halves, drop_seed_stride=stride, z_bound=z_bound, copy=copy)
-            return
-        for hv in range(self.halves):
-            ops.bn_fwd_infer(self._half(y, hv), A.param(f"{name}/gamma"), A.param(f"{name}/beta"), self.bn.mean[name],
-                             self.bn.var[name], self._half(z, hv), act=act, alpha=ALPHA, eps=BN_EPS)
-
-    def _bn_bwd(self, s, name, dz, z, y, dy, act, beta, ws, drop_rate=0.0, P=None, k=None):
-        """BN backward per half; the gamma/beta gradients of the halves accumulate.
-        P: the consuming conv's ConvPlanes (plane index k) -- when it keeps dy planes,
-        the BN backward writes them beside dy (no split pass before the conv's
-        backward GEMMs; fp16x3 planes with their bound into the conv's scale source)
-        and marks them ready."""
-        A = self.arena
-        feed = P is not None and P.dy is not None
-        ops.bn_bwd(dz, z, y, A.param(f"{name}/gamma"), s["mean"][name], s["inv"][name], dy, A.grad_of(f"{name}/gamma"),
-                   A.grad_of(f"{name}/beta"), act=act, alpha=ALPHA, drop_rate=drop_rate, beta=beta, ws=ws,
-                   dy_planes=plane_rows(P.dy, dy, 0) if feed else None, segments=self.halves,
-                   dy_fp32=not (feed and DY_PLANES_ONLY), dy_bound=self.gbound[k] if feed else None,
-                   offset=A.param(f"{name}/beta") if BN_RZ else None)
-        if feed:
-            P._filled(ops.TENSOR_DY)
+        self._bn_bwd(name, dz, z, y, dy, act, beta, ws, P, self.mean[name], self.inv[name],
+                     A.grad_of(f"{name}/gamma"), A.grad_of(f"{name}/beta"), self.halves, self.gbound[k], drop_rate)
 
     # backward ---------------------------------------------------------------
     def backward(self, dout, slot=0, beta=0.0, ws=None, drop_rate=DROP_RATE, on_grads_ready=None):
@@ -530,8 +535,8 @@ class GeneratorPlan:
             d = self.udesc[u]
             dy = self._dy(d, co)
             P = self._bwd_planes(8 + u)
-            self._bn_bwd(s, name, self.dcat[u][..., :co], s["cat"][u][..., :co], s["yu"][u], dy, "relu", beta, ws,
-                         drop_rate=drop_rate if drop else 0.0, P=P if FEED_DY else None, k=8 + u)
+            self._bn_bwd_block(8 + u, name, self.dcat[u][..., :co], s["cat"][u][..., :co], s["yu"][u], dy, "relu",
+                               beta, ws, P, drop_rate if drop else 0.0)
             hin = s["z8"] if u == 0 else s["cat"][u - 1]
             dhin = self.dz8 if u == 0 else self.dcat[u - 1]
             d.bwd_filter(hin, dy, A.grad_of(f"{name}/kernel"), beta=beta, ws=ws, planes=P)
@@ -547,7 +552,7 @@ class GeneratorPlan:
             dy = self._dy(d, co)
             P = self._bwd_planes(l)
             if bn:
-                self._bn_bwd(s, name, dz, z, s["yd"][l], dy, "lrelu", beta, ws, P=P if FEED_DY else None, k=l)
+                self._bn_bwd_block(l, name, dz, z, s["yd"][l], dy, "lrelu", beta, ws, P)
             elif masked_sum:
                 dy = dz   # (down2's input gradient applied act' to the summed gradient)
             else:
@@ -558,7 +563,7 @@ class GeneratorPlan:
             if l > 0:
                 # accumulate into the skip-gradient already sitting in the concat grad buffer; into
                 # a LeakyReLU block without BN (down1) with act' applied to the sum in the epilogue
-                if MASK_DZ and not self.downs[l - 1][3] and d.op_arith("bwd_data") != "fp32":
+                if not self.downs[l - 1][3] and d.op_arith("bwd_data") != "fp32":
                     d.bwd_data_masked_sum(dy, A.param(f"{name}/kernel"), self.dz_view(l - 1),
                                           self.z_view(s, l - 1), "lrelu", ALPHA, beta=1.0, ws=ws, planes=P)
                     masked_sum = True
@@ -593,7 +598,7 @@ def d_layout_order(width=1):
 # ---------------------------------------------------------------------------
 # PatchGAN discriminator plan (pix2pix.py:194-220)
 # ---------------------------------------------------------------------------
-class DiscriminatorPlan:
+class DiscriminatorPlan(_BlockPlan):
     """PatchGAN schedule.  halves=2 batches D([x, y]) (half 0, real) and
     D([x, G(x)]) (half 1, fake) into one pass over 2N images: the convs run
     once over both, BatchNorm per half (the reference's two separate calls);
@@ -636,47 +641,25 @@ class DiscriminatorPlan:
             self.dz = [_empty(d.out_shape, device) for d in self.desc[:-1]]
             maxdy = max(d.N * d.Ho * d.Wo * d.Cout for d in self.desc)
             self.dy = _empty((maxdy,), device)
-        # bf16x6 operand planes (see GeneratorPlan); the half-batch backward
-        # shares the weight planes and splits its own dy
-        if train:
-            self.planes = ops.plan_planes(self.desc, device)
-            # D.down1 (conv + LeakyReLU, no BN) writes D.down2's x planes in its epilogue
-            if FEED_X and self.planes[1].x is not None:
-                self.planes[0].fwd_out = self.planes[1].x
-            # (the half-batch pass runs on another stream beside the full backward and reads its
-            # weight planes with no event wait: it shares a layer's buffer only when the full
-            # pass's FORWARD splits the weights -- ready before either backward is enqueued; a
-            # layer whose weights the full pass splits first in a backward op gets a buffer of its
-            # own, split by the half pass itself)
+        # operand planes and their scale sources: D.down2's x planes from (max |input pair|,
+        # down1's weight bound), the x planes of the conv after BN block i from zb[i]
+        self._wire_planes(self.desc, device, train)
+        self.planes_half, self.gbound_h = self.planes, self.gbound
+        if self.desc_half is not self.desc:
+            # the half-batch backward (the G path through D(fake)) shares the weight planes and has
+            # its own dy planes and bounds, dz and dy scratch, so the two backwards may run
+            # concurrently on two streams (trainer.Pix2PixTrainer).  (It reads the weight planes
+            # with no event wait: it shares a layer's buffer only when the full pass's FORWARD
+            # splits the weights -- ready before either backward is enqueued; a layer whose weights
+            # the full pass splits first in a backward op gets a buffer of its own, split by the
+            # half pass itself)
             wshare = [p.w if (p.w is not None and d.plane_mask[ops.OP_FWD] & ops.TENSOR_W) else None
                       for p, d in zip(self.planes, self.desc)]
-            self.planes_half = (ops.plan_planes(self.desc_half, device, keep_x=False, wbufs=wshare)
-                                if self.desc_half is not self.desc else self.planes)
-            # one dy bound per layer for the full backward; the half-batch backward (the G path
-            # through D(fake)) has its own bounds, dz and dy scratch, so the two backwards may run
-            # concurrently on two streams (trainer.Pix2PixTrainer overlap)
-            self.gbound = grad_bounds(self.desc, self.planes, device)
-            self.gbound_h = list(self.gbound)
-            # fp16x3 activation planes scaled from their producers' bounds (ActBounds): D.down1's
-            # conv output from (max |input pair|, down1's weight bound), BN block i's output zb[i]
-            self.ab = None
-            if ACT_BOUNDS and any(x3_planes(P) for P in self.planes):
-                self.ab = ActBounds(len(self.desc), device)
-                for k, d in enumerate(self.desc):
-                    if x3_planes(self.planes[k]):
-                        d.set_act_scale(x=self.ab.first_src if k == 1 else self.ab.zb[k - 1])
-                if x3_planes(self.planes[1]) and FEED_X:
-                    self.desc[0].set_act_scale(y=self.ab.first_src)
-            if self.desc_half is not self.desc:
-                for i, (d, P) in enumerate(zip(self.desc_half, self.planes_half)):
-                    if FEED_DY and P is not None and P.dy is not None and P.dy.fmt == ops.PLANES_F16X3:
-                        self.gbound_h[i] = ops.max_slot(device=device)
-                        d.set_grad_scale(dy_m=self.gbound_h[i])
-                self.dz_h = [_empty(d.out_shape, device) for d in self.desc_half[:-1]]
-                self.dy_h = _empty((max(d.N * d.Ho * d.Wo * d.Cout for d in self.desc_half),), device)
-        else:
-            self.planes = self.planes_half = [None] * len(self.desc)
-            self.ab = None
+            self.planes_half = ops.plan_planes(self.desc_half, device, keep_x=False, wbufs=wshare)
+            own = grad_bounds(self.desc_half, self.planes_half, device)
+            self.gbound_h = [h if h is not None else b for h, b in zip(own, self.gbound)]
+            self.dz_h = [_empty(d.out_shape, device) for d in self.desc_half[:-1]]
+            self.dy_h = _empty((max(d.N * d.Ho * d.Wo * d.Cout for d in self.desc_half),), device)
         # G path (train_pix2pix.py:64): of dL/d D([inp, G(x)]) only the G(x) channels 3..5
         # are used, so that input gradient runs as a Cin-3 conv over down1's filter slice
         # w[:, :, 3:6, :] (copied per step) straight into dL/dG(x) (beta 1); per channel the
@@ -695,9 +678,6 @@ class DiscriminatorPlan:
     def slots(self):
         return [{"inp": self.inp, "logits": self.logits}]
 
-    def _half(self, t, h):
-        return t[h * self.N:(h + 1) * self.N]
-
     def _dy(self, d, buf=None):
         buf = self.dy if buf is None else buf
         return buf[: d.N * d.Ho * d.Wo * d.Cout].view(d.N, d.Ho, d.Wo, d.Cout)
@@ -705,10 +685,8 @@ class DiscriminatorPlan:
     def forward(self, slot=0, training=True, ws=None):
         A = self.arena
         h = self.inp
-        for p in self.planes:
-            if p is not None:
-                p.invalidate(ops.TENSOR_X | ops.TENSOR_W)
-        if self.planes_half is not self.planes:
+        planes = self._fwd_planes()
+        if self.planes_half is not planes:
             # (the half-batch backward shares a layer's weight planes only where its descriptor
             # has the same plane layout; a buffer of its own is split by its bwd_data)
             for p in self.planes_half:
@@ -719,7 +697,7 @@ class DiscriminatorPlan:
             ab.first_conv(self.inp, A.param("down1/kernel"))   # D.down2's x planes: (max |inp|, down1's bound)
         for i, (name, ci, co, bn) in enumerate(self.specs):
             d = self.desc[i]
-            P = self.planes[i]
+            P = planes[i]
             if name == "last":
                 d.fwd(h, A.param("last/kernel"), self.logits, bias=A.param("last/bias"), ws=ws, planes=P)
                 return self.logits
@@ -729,23 +707,10 @@ class DiscriminatorPlan:
             else:
                 y = self.y[i]
                 d.fwd(h, A.param(f"{name}/kernel"), y, ws=ws, planes=P)
-                # z feeds the next conv's kept x planes (training)
-                Pn = self.planes[i + 1]
-                xp = Pn.x if FEED_X and training and Pn is not None else None
-                if training:   # one segmented call: real and fake normalised separately, moving stats in order
-                    rows = z[..., 0].numel()
-                    ops.bn_fwd_train(y, A.param(f"{name}/gamma"), A.param(f"{name}/beta"), self.mean[name],
-                                     self.inv[name], self.bn.mean[name], self.bn.var[name], z, act="lrelu",
-                                     alpha=ALPHA, momentum=BN_MOMENTUM, eps=BN_EPS, ws=ws,
-                                     z_planes=[zplanes(xp, rows, co, 0)] if xp is not None else (),
-                                     segments=self.halves, z_bound=ab.zb[i] if ab is not None else None)
-                else:
-                    for hv in range(self.halves):
-                        ops.bn_fwd_infer(self._half(y, hv), A.param(f"{name}/gamma"), A.param(f"{name}/beta"),
-                                         self.bn.mean[name], self.bn.var[name], self._half(z, hv), act="lrelu",
-                                         alpha=ALPHA, eps=BN_EPS)
-                if xp is not None:
-                    Pn._filled(ops.TENSOR_X)
+                # z feeds the next conv's kept x planes (training); real and fake normalised separately
+                Pn = planes[i + 1]
+                outs = [(i + 1, co, 0)] if training and Pn is not None and Pn.x is not None else []
+                self._bn_fwd(name, y, z, "lrelu", training, ws, outs, z_bound=ab.zb[i] if ab is not None else None)
             h = z
 
     def backward(self, dlogits, slot=0, param_grads=True, beta=0.0, input_grad=None, input_beta=0.0, ws=None,
@@ -771,7 +736,6 @@ class DiscriminatorPlan:
         dybuf = self.dy_h if own else None
         gb = self.gbound_h if own else self.gbound
         dh = dlogits
-        masked = False   # dh already carries act'(z) of this layer's LeakyReLU (see bwd_data_masked below)
         n = len(self.specs)
         for i in range(n - 1, -1, -1):
             name, ci, co, bn = self.specs[i]
@@ -787,23 +751,14 @@ class DiscriminatorPlan:
             else:
                 dy = self._dy(d, dybuf)
                 if bn:
-                    feed = FEED_DY and P is not None and P.dy is not None
                     # all halves in one segmented call, or the one half's statistics
                     mean = self.mean[name] if half is None else self.mean[name][half]
                     inv = self.inv[name] if half is None else self.inv[name][half]
-                    ops.bn_bwd(dh, sub(self.z[i]), sub(self.y[i]), A.param(f"{name}/gamma"), mean, inv, dy,
-                               A.grad_of(f"{name}/gamma") if param_grads else None,
-                               A.grad_of(f"{name}/beta") if param_grads else None, act="lrelu", alpha=ALPHA,
-                               beta=beta, ws=ws, dy_planes=plane_rows(P.dy, dy, 0) if feed else None,
-                               segments=len(hs), dy_fp32=not (feed and DY_PLANES_ONLY),
-                               dy_bound=gb[i] if feed else None,
-                               offset=A.param(f"{name}/beta") if BN_RZ else None)
-                    if feed:
-                        P._filled(ops.TENSOR_DY)
-                elif masked:
-                    dy = dh
+                    self._bn_bwd(name, dh, sub(self.z[i]), sub(self.y[i]), dy, "lrelu", beta, ws, P, mean, inv,
+                                 A.grad_of(f"{name}/gamma") if param_grads else None,
+                                 A.grad_of(f"{name}/beta") if param_grads else None, len(hs), gb[i])
                 else:
-                    ops.act_bwd(dh, sub(self.z[i]), dy, "lrelu", ALPHA)
+                    dy = dh   # (down1: the input gradient above applied its act', bwd_data_masked below)
                 if param_grads:
                     hin = sub(self.inp) if i == 0 else sub(self.z[i - 1])
                     d.bwd_filter(hin, dy, A.grad_of(f"{name}/kernel"), beta=beta, ws=ws, planes=P)
@@ -813,8 +768,7 @@ class DiscriminatorPlan:
                 dz = dzs[i - 1] if own else sub(self.dz[i - 1])
                 # a LeakyReLU block without BN below (down1, pix2pix.py:118-121): its act' applied
                 # in this input gradient's epilogue -- no separate act_bwd pass over dz
-                masked = MASK_DZ and not self.specs[i - 1][3]
-                if masked:
+                if not self.specs[i - 1][3]:
                     d.bwd_data_masked(dy, A.param(f"{name}/kernel"), dz, sub(self.z[i - 1]), "lrelu", ALPHA, ws=ws,
                                       planes=P)
                 else:

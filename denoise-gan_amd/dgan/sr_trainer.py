@@ -195,8 +195,7 @@ COEF = {
 # the target's work (its VGG19 features and D(real)) on a second stream beside G's forward,
 # which it does not need -- for outputs of >= 256^2 pixels: FastSRGAN 512^2 +1.7 %, while the
 # 96^2 SRGAN (-2.5 %) and the 64^2 autoencoder (-7 %) lose more to the halved VGG19 batch than
-# the overlap returns (profiles/r5/ab_sr_overlap.txt; DG_SR_NO_OVERLAP: never)
-SR_OVERLAP = not os.environ.get("DG_SR_NO_OVERLAP")
+# the overlap returns (profiles/r5/ab_sr_overlap.txt)
 SR_OVERLAP_MIN_PIXELS = 256 * 256
 
 LOSS_SCALE_INIT = 2.0 ** 15     # tf.keras DynamicLossScale defaults (srgan.py:64-67)
@@ -238,7 +237,7 @@ class SRTrainer:
         self.dgen = e((N, H, W, 3))
         self.loss = torch.zeros(7, dtype=torch.float32, device=device)
         dev = torch.device(device)
-        ov = SR_OVERLAP and dev.type == "cuda" and H * W >= SR_OVERLAP_MIN_PIXELS
+        ov = dev.type == "cuda" and H * W >= SR_OVERLAP_MIN_PIXELS
         self.content = ContentLoss(vgg, N, H, W, device, split=ov) if vgg is not None else None
         wsb = [self.Gp.ws_bytes, self.Dp.ws_bytes, ops.gan_loss_workspace_bytes()]
         if self.content:

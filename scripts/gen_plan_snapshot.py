@@ -178,8 +178,8 @@ def geometries():
     g = []
     # pix2pix bs16 (bench.py): G over [x; y] and D over [real; fake] at 2N = 32, D's fake half and
     # the generator's first layer at N = 16; VGG19 at 256^2 (sr_trainer.ContentLoss): one forward
-    # over [generated; target] at 2N, or the two halves' forwards at N (trainer.OVERLAP_VT, the
-    # default), and the backward through the generated half at N
+    # over [generated; target] at 2N, or the two halves' forwards at N (ContentLoss(split=True),
+    # what the pix2pix trainer builds), and the backward through the generated half at N
     g += unet(32, 256, 256) + patchgan(32, 256) + patchgan(16, 256) + [(16, 256, 256, 3, 64, 4, 2, "same", False)]
     g += vgg19(32, 256) + vgg19(16, 256)
     # SRGAN 24 -> 96 bs32: D over the generated and real batches (N, and both at 2N), VGG19 as above
