@@ -147,6 +147,10 @@ _SIGS = {
     "dg_bn_fold": (c_int, [c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_float, _P, _P, _P, _P]),
     "dg_u8_stage": (c_int, [c_int] * 12 + [_P, _P, _P]),
     "dg_u8_unstage": (c_int, [c_int] * 13 + [_P, _P, _P]),
+    "dg_dwconv3_fwd_act": (c_int, [c_int, c_int, c_int, c_int, _P, c_int, _P, _P, c_int, c_float, _P, c_int, _P]),
+    "dg_mbconv_supported": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "dg_mbconv_tile": (c_int, [ctypes.POINTER(c_int)]),
+    "dg_mbconv_fwd": (c_int, [c_int] * 6 + [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, _P]),
     "dg_u8_err_sums": (c_int, [c_int, c_int64, _P, _P, _P, _P]),
     "dg_err_sums_workspace_size": (c_int, [c_int, c_int64, ctypes.POINTER(c_size_t)]),
     "dg_f32_err_sums": (c_int, [c_int, c_int64, _P, _P, _P, _P, c_size_t, _P]),

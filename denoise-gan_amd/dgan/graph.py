@@ -124,13 +124,29 @@ class Graph:
     def upsample_relu(self, x, name=None):
         return self._node("upsample", self._uname(name or "up_sampling2d"), [x], x.C)
 
-    def dwconv(self, x, use_bias=True, kernel_init=("glorot_uniform",), name=None):
-        """keras.layers.DepthwiseConv2D(3, strides 1, 'same')."""
+    def dwconv(self, x, use_bias=True, kernel_init=("glorot_uniform",), act=None, alpha=0.3, name=None):
+        """keras.layers.DepthwiseConv2D(3, strides 1, 'same'); act: a fused activation (inference
+        graphs only: the BN-folded form of dwconv -> BN -> act, dgan/sr_infer.py)."""
         name = self._uname(name or "depthwise_conv2d")
         self._var(f"{name}/depthwise_kernel", (3, 3, x.C, 1), kernel_init)
         if use_bias:
             self._var(f"{name}/bias", (x.C,), ("zeros",))
-        return self._node("dwconv", name, [x], x.C, bias=use_bias)
+        return self._node("dwconv", name, [x], x.C, bias=use_bias, act=act, alpha=alpha)
+
+    def mbconv(self, x, expanded, filters, expand, depthwise, project, res=False, name=None):
+        """The fused inverted-residual block of an inference graph (dgan/sr_infer.py fold_graph):
+        conv 1x1 + ReLU -> dwconv + ReLU -> conv 1x1 [+ x], one dg_mbconv_fwd.  expand / depthwise /
+        project: the layer names its six variables keep (all three layers biased)."""
+        self._var(f"{expand}/kernel", (1, 1, x.C, expanded), ("glorot_uniform",))
+        self._var(f"{expand}/bias", (expanded,), ("zeros",))
+        self._var(f"{depthwise}/depthwise_kernel", (3, 3, expanded, 1), ("glorot_uniform",))
+        self._var(f"{depthwise}/bias", (expanded,), ("zeros",))
+        self._var(f"{project}/kernel", (1, 1, expanded, filters), ("glorot_uniform",))
+        self._var(f"{project}/bias", (filters,), ("zeros",))
+        if res and filters != x.C:
+            raise ValueError("a residual mbconv needs equal channels")
+        return self._node("mbconv", self._uname(name or "mbconv"), [x], filters, E=expanded, expand=expand,
+                          depthwise=depthwise, project=project, res=bool(res))
 
     def act(self, x, act, alpha=0.3, name=None):
         return self._node("act", self._uname(name or "activation"), [x], x.C, act=act, alpha=alpha)
@@ -298,7 +314,13 @@ class GraphPlan:
                 if y != x:
                     raise ValueError(f"add {n.name}: shape mismatch {x} vs {y}")
                 shp[n.out.id] = x
+            elif n.kind == "mbconv":
+                if self.train:
+                    raise ValueError(f"mbconv {n.name}: a fused block belongs to an inference graph (no backward)")
+                shp[n.out.id] = (N, h, w, n.out.C)
             else:  # bn, dwconv, act
+                if n.kind == "dwconv" and self.train and ops.act_id(n.attrs.get("act")) != 0:
+                    raise ValueError(f"dwconv {n.name}: a fused activation belongs to an inference graph (no backward)")
                 shp[n.out.id] = x
         self.shape = shp
         self.out_shape = shp[graph.output.id]
@@ -935,7 +957,16 @@ class GraphPlan:
                 ops.upsample2_relu_fwd(xin, y)
             elif k == "dwconv":
                 bias = A.param(f"{n.name}/bias") if n.attrs["bias"] else None
-                ops.dwconv3_fwd(xin, A.param(f"{n.name}/depthwise_kernel"), y, bias=bias)
+                if ops.act_id(n.attrs.get("act")) != 0:
+                    ops.dwconv3_fwd_act(xin, A.param(f"{n.name}/depthwise_kernel"), y, bias=bias, act=n.attrs["act"],
+                                        alpha=n.attrs["alpha"])
+                else:
+                    ops.dwconv3_fwd(xin, A.param(f"{n.name}/depthwise_kernel"), y, bias=bias)
+            elif k == "mbconv":
+                e, d, p = n.attrs["expand"], n.attrs["depthwise"], n.attrs["project"]
+                ops.mbconv_fwd(xin, A.param(f"{e}/kernel"), A.param(f"{e}/bias"), A.param(f"{d}/depthwise_kernel"),
+                               A.param(f"{d}/bias"), A.param(f"{p}/kernel"), A.param(f"{p}/bias"), y,
+                               res=xin if n.attrs["res"] else None)
             elif k == "act":
                 ops.act_fwd(xin, y, n.attrs["act"], n.attrs["alpha"])
             else:
@@ -1206,6 +1237,12 @@ class GraphNetwork:
         ws.get(p.ws_bytes)
         y = p.forward(x, slot=0, training=training, ws=ws)
         return y.contiguous().clone()
+
+    def predict(self, x, batch_size=None):
+        """Keras `model.predict`: numpy in, numpy out, on the BN-folded inference path
+        (dgan/sr_infer.py) with the current weights."""
+        from .sr_infer import predict
+        return predict(self, x, batch_size)
 
     # weights -------------------------------------------------------------
     def state_dict(self):

@@ -979,6 +979,51 @@ def dwconv3_fwd(x, k, y, bias=None):
     return y
 
 
+def dwconv3_fwd_act(x, k, y, bias=None, act="none", alpha=0.3):
+    """y = act(bias + dwconv3(x)) (dg_dwconv3_fwd_act): a BN-folded DepthwiseConv2D and the
+    activation that followed its BatchNorm."""
+    N, H, W, C = _nhwc(x)
+    call("dg_dwconv3_fwd_act", N, H, W, C, _p(x), pix_ld(x, C), _p(k), _p(bias), act_id(act), float(alpha), _p(y),
+         pix_ld(y, C), _stream())
+    return y
+
+
+# channel counts the Python side may ask about without the library (fold_graph runs on the CPU):
+# include/dgan.h dg_mbconv_supported, checked against it by tests/test_sr_infer_gpu.py
+MBCONV_C, MBCONV_E_MAX = 32, 192
+
+
+def mbconv_supported(C, E, Co):
+    return C == MBCONV_C and Co == MBCONV_C and E % MBCONV_C == 0 and MBCONV_C <= E <= MBCONV_E_MAX
+
+
+def mbconv_supported_lib(C, E, Co):
+    ok = ctypes.c_int()
+    call("dg_mbconv_supported", int(C), int(E), int(Co), ctypes.byref(ok))
+    return bool(ok.value)
+
+
+def mbconv_tile():
+    t = ctypes.c_int()
+    call("dg_mbconv_tile", ctypes.byref(t))
+    return t.value
+
+
+def mbconv_fwd(x, w_exp, b_exp, k_dw, b_dw, w_proj, b_proj, y, res=None):
+    """The fused inverted-residual block (dg_mbconv_fwd): x [N,H,W,C], w_exp [...,C,E], k_dw
+    [3,3,E,1], w_proj [...,E,Co] (dense Keras kernels), res None or [N,H,W,Co] (may be x)."""
+    N, H, W, C = _nhwc(x)
+    E, Co = w_exp.shape[-1], w_proj.shape[-1]
+    for t in (w_exp, k_dw, w_proj):
+        if not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda:
+            raise DGError("mbconv_fwd: dense fp32 device kernels")
+    if w_exp.numel() != C * E or k_dw.numel() != 9 * E or w_proj.numel() != E * Co or tuple(y.shape) != (N, H, W, Co):
+        raise DGError("mbconv_fwd: shapes do not match")
+    call("dg_mbconv_fwd", N, H, W, C, E, Co, _p(x), pix_ld(x, C), _p(w_exp), _p(b_exp), _p(k_dw), _p(b_dw), _p(w_proj),
+         _p(b_proj), _p(res), pix_ld(res, Co) if res is not None else 0, _p(y), pix_ld(y, Co), _stream())
+    return y
+
+
 def dwconv3_bwd_data(dy, k, dx, beta=0.0):
     N, H, W, C = _nhwc(dy)
     call("dg_dwconv3_bwd_data", N, H, W, C, _p(dy), pix_ld(dy, C), _p(k), _p(dx), pix_ld(dx, C), float(beta),

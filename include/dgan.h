@@ -613,6 +613,29 @@ int dg_u8_unstage(int n, int h, int w, int Th, int Tw, int Sh, int Sw, int oy, i
                   int margin_left, const float *tiles, unsigned char *out, dg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Super-resolution inference (the FastSRGAN generator of the reference's infer_video.py with
+ * its BatchNorms folded, dgan/sr_infer.py).
+ * ---------------------------------------------------------------------- */
+/* dg_dwconv3_fwd followed by an activation of the sum: y = act(b + dw3x3_same(x)).  With
+ * DG_ACT_NONE the result equals dg_dwconv3_fwd's bit for bit. */
+int dg_dwconv3_fwd_act(int N, int H, int W, int C, const float *x, int ldx, const float *k, const float *bias,
+                       int act, float alpha, float *y, int ldy, dg_stream_t stream);
+/* The fused inverted-residual block, fp32 throughout (v_mfma_f32_32x32x2_f32 and fp32 FMAs):
+ *   y[n,h,w,:] = b_proj + W_proj^T relu(b_dw + dw3x3_same(mask relu(b_exp + W_exp^T x))) [+ res[n,h,w,:]]
+ * x [N,H,W,C], w_exp [C][E], k_dw [9][E], w_proj [E][Co], y [N,H,W,Co]; biases may be NULL (0),
+ * res may be NULL or x.  mask: the depthwise input is zero outside the image (Keras pads the
+ * depthwise INPUT; it is not relu(b_exp), the expansion of a zero-padded x).  No intermediate is
+ * written to memory.  Pixel strides are multiples of 4 floats, x / y / res 16-byte aligned.
+ * DG_ERR_ARG for channel counts dg_mbconv_supported refuses and when y shares memory with x
+ * (neighbouring workgroups read x's halo).  dg_mbconv_tile: the edge of the square output tile
+ * one workgroup computes. */
+int dg_mbconv_supported(int C, int E, int Co, int *ok);
+int dg_mbconv_tile(int *tile);
+int dg_mbconv_fwd(int N, int H, int W, int C, int E, int Co, const float *x, int ldx, const float *w_exp,
+                  const float *b_exp, const float *k_dw, const float *b_dw, const float *w_proj, const float *b_proj,
+                  const float *res, int ldres, float *y, int ldy, dg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Image quality metrics (the tf.image.psnr / tf.image.ssim defaults, accumulated in fp64; the
  * reference has none).  Images are dense device tensors [n][h][w][C], uint8 or fp32, of any byte
  * alignment.  Results are per image.  No floating-point atomics: a result depends on the shapes
