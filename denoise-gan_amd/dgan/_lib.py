@@ -157,6 +157,8 @@ _SIGS = {
     "dg_ssim_workspace_size": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "dg_ssim_u8": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_double, _P, _P, c_size_t, _P]),
     "dg_ssim_f32": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
+    "dg_resize_u8": (c_int, [c_int] * 6 + [_P] * 6 + [c_double, c_double, _P]),
+    "dg_resize_f32": (c_int, [c_int] * 6 + [_P] * 6 + [_P]),
 }
 
 EXPORTED = tuple(_SIGS)
@@ -171,6 +173,10 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise DGError(f"libdgan.so not found at {LIB_PATH}: run `python __graft_entry__.py` (build) first")
+        # torch first: a torch wheel that bundles its own HIP runtime must be the one the library
+        # binds to; loaded the other way round the process holds two runtimes and the library's
+        # launches find no device
+        import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
             fn = getattr(L, name)

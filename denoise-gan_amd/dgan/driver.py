@@ -66,11 +66,14 @@ def sync_before_save(model):
         sync_bn_stats(model)
 
 
-def log_quality(writer, args, gen, y, step):
+def log_quality(writer, args, gen, y, step, x=None):
     """With `metrics` set in the driver's params: PSNR and SSIM (dgan.metrics, on the device) of the
     inference output `gen` the image summary already computed against the clean batch `y`, both
     [-1, 1] read on [0, 1] (scale 0.5, shift 0.5, max_val 1); the batch means go to the summary
-    as Quality/psnr and Quality/ssim.  Reads only: no training state changes."""
+    as Quality/psnr and Quality/ssim.  With the low-resolution input batch `x` (smaller than `y`)
+    the bicubic baseline is scored the same way: dgan.resize of x to y's size, clamped to
+    [-1, 1], as Quality/psnr_bicubic and Quality/ssim_bicubic.  Reads only: no training state
+    changes."""
     if not getattr(args, "metrics", 0):
         return
     from . import metrics
@@ -82,6 +85,13 @@ def log_quality(writer, args, gen, y, step):
     ssim = metrics.ssim(gen, y, max_val=1.0, scale=0.5, shift=0.5).mean()
     writer.scalar("Quality/psnr", psnr.item(), step=step)
     writer.scalar("Quality/ssim", ssim.item(), step=step)
+    if x is not None and x.shape[1] < y.shape[1] and x.shape[2] < y.shape[2]:
+        from .resize import resize
+        base = resize(to_device(x, gen.device).contiguous(), y.shape[1], y.shape[2]).clamp_(-1.0, 1.0)
+        psnr = metrics.psnr(base, y, max_val=2.0).mean()
+        ssim = metrics.ssim(base, y, max_val=1.0, scale=0.5, shift=0.5).mean()
+        writer.scalar("Quality/psnr_bicubic", psnr.item(), step=step)
+        writer.scalar("Quality/ssim_bicubic", ssim.item(), step=step)
 
 
 def run(args, model, ds, train, save_final=None):

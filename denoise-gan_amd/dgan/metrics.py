@@ -8,7 +8,9 @@ c2 = (0.03 max_val)^2, the mean of l * cs over the (h-10) x (w-10) map and the c
 `psnr_ref` / `ssim_ref` are pure numpy (fp64) and import neither torch nor the library: the tests
 and the host timings use them.  `psnr` / `ssim` run on the device (csrc/metrics.hip) on dense uint8
 or fp32 NHWC tensors and return device fp64 tensors without a host synchronisation; `Evaluator`
-scores a `Denoiser`'s input and output frame against a clean frame where they already are.
+scores a `Denoiser`'s input and output frame against a clean frame where they already are, and
+`SREvaluator` an `Upscaler`'s output and the bicubic baseline (dgan/resize.py) against the
+high-resolution original.
 """
 import numpy as np
 
@@ -230,3 +232,86 @@ class Evaluator:
         ssim(f.u8_out, ref, out=res[3])
         r = res.cpu().numpy()
         return {k: r[i] for i, k in enumerate(SCORES)}
+
+
+SR_SCORES = ("psnr_bicubic", "psnr_upscaled", "ssim_bicubic", "ssim_upscaled")
+
+
+class SREvaluator:
+    """Scores an `Upscaler` against high-resolution originals on the device: the original is
+    uploaded, degraded by a resize (dgan.resize, the degrade conversion) straight into the
+    Upscaler frame's `u8_in`, upscaled into `u8_out`, and the same low-resolution frame resized
+    back (the display conversion) is the baseline; both are scored against the original and only
+    the 4 n scalars come back.  `method` names the resize of both directions.  With a
+    graph-capturing `Upscaler` the resizes and the metrics run eagerly around the replay.
+    jpeg_quality Q adds the one host step: the low-resolution frame comes back, goes through
+    Pillow's JPEG codec at quality Q with 4:2:0 subsampling (dataloader.jpeg_roundtrip on uint8)
+    and is uploaded again."""
+
+    MAX_SHAPES = 4   # (original, baseline, scores) triples kept, least recently used first out
+
+    def __init__(self, upscaler, method="bicubic", jpeg_quality=None):
+        from .resize import METHODS
+        if method not in METHODS:
+            raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+        if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
+            raise ValueError(f"jpeg_quality must be in 1..100, got {jpeg_quality}")
+        self.upscaler, self.method = upscaler, method
+        self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
+        self._bufs = {}
+
+    def buffers(self, shape):
+        """(the device uint8 original, the device uint8 baseline, the device fp64 scores [4, n] in
+        SR_SCORES order) of one image shape (n, H, W, 3): what the last `evaluate` of that shape left."""
+        import torch
+        dev = self.upscaler.device
+        return _lru(self._bufs, tuple(shape),
+                    lambda: (torch.empty(shape, dtype=torch.uint8, device=dev),
+                             torch.empty(shape, dtype=torch.uint8, device=dev),
+                             torch.empty((len(SR_SCORES), shape[0]), dtype=torch.float64, device=dev)), self.MAX_SHAPES)
+
+    def _jpeg(self, low):
+        """The host step: every image of the device frame `low` through the JPEG codec, in place."""
+        import io
+        import torch
+        from PIL import Image
+        host = low.cpu().numpy()
+        for i in range(host.shape[0]):
+            buf = io.BytesIO()
+            Image.fromarray(host[i], "RGB").save(buf, format="JPEG", quality=self.jpeg_quality, subsampling=2)
+            buf.seek(0)
+            host[i] = np.asarray(Image.open(buf).convert("RGB"), np.uint8)
+        low.copy_(torch.from_numpy(host))
+
+    def evaluate(self, hr_u8):
+        """uint8 [n,H,W,3] (or [H,W,3]) originals, H and W multiples of the scale and at least 11
+        -> {"psnr_bicubic", "psnr_upscaled", "ssim_bicubic", "ssim_upscaled"}: fp64 numpy arrays
+        [n] (max_val 255)."""
+        import torch
+        from .resize import DEGRADE, DISPLAY, resize
+        hr = np.asarray(hr_u8)
+        if hr.ndim == 3:
+            hr = hr[None]
+        if hr.dtype != np.uint8 or hr.ndim != 4 or hr.shape[-1] != 3:
+            raise ValueError(f"evaluate expects uint8 [n,H,W,3] or [H,W,3], got {hr.dtype} {hr.shape}")
+        n, H, W = hr.shape[:3]
+        s = self.upscaler.scale
+        if H % s or W % s or min(H, W) < SSIM_TAPS:
+            raise ValueError(f"evaluate: images of {H}x{W} must be multiples of the scale {s} and at least "
+                             f"{SSIM_TAPS}x{SSIM_TAPS}")
+        if n == 0:
+            return {k: np.zeros(0) for k in SR_SCORES}
+        f = self.upscaler.frame(n, H // s, W // s)
+        ref, base, res = self.buffers(tuple(hr.shape))
+        ref.copy_(torch.from_numpy(np.ascontiguousarray(hr)))
+        resize(ref, H // s, W // s, self.method, *DEGRADE, out=f.u8_in)
+        if self.jpeg_quality is not None:
+            self._jpeg(f.u8_in)
+        self.upscaler.run_frame(f)
+        resize(f.u8_in, H, W, self.method, *DISPLAY, out=base)
+        psnr(base, ref, out=res[0])
+        psnr(f.u8_out, ref, out=res[1])
+        ssim(base, ref, out=res[2])
+        ssim(f.u8_out, ref, out=res[3])
+        r = res.cpu().numpy()
+        return {k: r[i] for i, k in enumerate(SR_SCORES)}

@@ -1194,3 +1194,34 @@ def ssim(a, b, out, ws, max_val, scale=1.0, shift=0.0):
         call("dg_ssim_f32", n, h, w, C, _p(a), _p(b), float(scale), float(shift), float(max_val), _p(out), wp, wn,
              _stream())
     return out
+
+
+# ---- image resize (include/dgan.h "Image resize") ------------------------------------------------
+def resize(x, out, iy, wy, ix, wx, mul=1.0, bias=0.0):
+    """out[n,ho,wo,C] = the 4-tap resize of the dense uint8 (dg_resize_u8, written as
+    floor(clamp(v * mul + bias, 0, 255))) or fp32 (dg_resize_f32) images x[n,hi,wi,C]; iy / wy
+    [ho,4] and ix / wx [wo,4]: the device tap tables (int32 / float64) of dgan.resize.resize_taps."""
+    for t in (x, out):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.uint8, torch.float32):
+            raise DGError(f"resize: expected uint8 or float32 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 4 or not t.is_contiguous():
+            raise DGError(f"resize: expected dense [n,h,w,C] tensors, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise DGError("resize: expected device tensors (the HIP path has no CPU fallback)")
+    n, hi, wi, C = x.shape
+    ho, wo = out.shape[1:3]
+    if out.dtype != x.dtype or out.shape[0] != n or out.shape[3] != C:
+        raise DGError(f"resize: the output {out.dtype} {tuple(out.shape)} does not match the input {x.dtype} "
+                      f"{tuple(x.shape)}")
+    _metric_buf(iy, torch.int32, 4 * ho, "resize iy")
+    _metric_buf(wy, torch.float64, 4 * ho, "resize wy")
+    _metric_buf(ix, torch.int32, 4 * wo, "resize ix")
+    _metric_buf(wx, torch.float64, 4 * wo, "resize wx")
+    if x.dtype == torch.uint8:
+        call("dg_resize_u8", n, hi, wi, C, ho, wo, _p(x), _p(out), _p(iy), _p(wy), _p(ix), _p(wx), float(mul),
+             float(bias), _stream())
+    else:
+        if mul != 1.0 or bias != 0.0:
+            raise DGError("resize: mul / bias apply to uint8 images only")
+        call("dg_resize_f32", n, hi, wi, C, ho, wo, _p(x), _p(out), _p(iy), _p(wy), _p(ix), _p(wx), _stream())
+    return out

@@ -374,7 +374,8 @@ class Upscaler:
     def geometry(self, h, w):
         return sr_tile_geometry(h, w, self.multiple, self.tile, self.margin)
 
-    def _frame(self, n, h, w):
+    def frame(self, n, h, w):
+        """The buffers of n images of h x w (made, and with graph=True captured, on first use)."""
         import torch
         key = (n, h, w)
         if key in self._frames:
@@ -429,8 +430,13 @@ class Upscaler:
         without reading anything back: the frame whose device buffers `u8_in` / `u8_out` hold the
         input and the result until the next call on the same shape."""
         import torch
-        f = self._frame(*images.shape[:3])
+        f = self.frame(*images.shape[:3])
         f.u8_in.copy_(torch.from_numpy(np.ascontiguousarray(images)))
+        return self.run_frame(f)
+
+    def run_frame(self, f):
+        """Upscale what the frame's `u8_in` holds into its `u8_out` on the current stream (a replay
+        of the captured graph where there is one); returns the frame."""
         if f.graph is not None:
             f.graph.replay()
         else:

@@ -44,7 +44,7 @@ def train(model, dataset, args, writer):
                 gen = model.generator(x, training=False)
                 writer.image("Images/Generated", (255 * (gen.cpu().numpy() + 1) / 2).astype(np.uint8),
                              step=model.iterations)
-                driver.log_quality(writer, args, gen, y, step=model.iterations)
+                driver.log_quality(writer, args, gen, y, step=model.iterations, x=x)
                 writer.flush()
 
 

@@ -663,6 +663,22 @@ int dg_ssim_u8(int n, int h, int w, int C, const unsigned char *a, const unsigne
 int dg_ssim_f32(int n, int h, int w, int C, const float *a, const float *b, double scale, double shift,
                 double max_val, double *out, void *ws, size_t ws_bytes, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Image resize by 4-tap tables (dgan/resize.py resize_taps: tf.image.resize 'bicubic' /
+ * 'bilinear', half-pixel centres, no antialiasing).  Dense NHWC images [n][hi][wi][C] ->
+ * [n][ho][wo][C], any C >= 1, any byte alignment.  iy / wy [ho][4] and ix / wx [wo][4] are the
+ * device tables of tap rows / columns and their fp64 weights; the kernel clamps every index into
+ * the image.  fp64 in a fixed order, every product and sum rounded on its own (no FMA):
+ *   t = ((wy0 a[iy0] + wy1 a[iy1]) + wy2 a[iy2]) + wy3 a[iy3]     per input column, then
+ *   v = ((wx0 t[ix0] + wx1 t[ix1]) + wx2 t[ix2]) + wx3 t[ix3];
+ * dg_resize_u8 writes floor(clamp(v * mul + bias, 0, 255)), dg_resize_f32 writes (float)v.  One
+ * launch, no workspace; `in` and `out` must not be the same buffer. */
+int dg_resize_u8(int n, int hi, int wi, int C, int ho, int wo, const unsigned char *in, unsigned char *out,
+                 const int *iy, const double *wy, const int *ix, const double *wx, double mul, double bias,
+                 dg_stream_t stream);
+int dg_resize_f32(int n, int hi, int wi, int C, int ho, int wo, const float *in, float *out, const int *iy,
+                  const double *wy, const int *ix, const double *wx, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
