@@ -591,6 +591,9 @@ k_narrow_dgrad(const GemmArgs p, int w_in_lds) {
     const int h = hh * g.sh + ph.ph, w = ww * g.sw + ph.pw;
     const int Ci = g.Ci, Co = g.Co;
     float acc[NARROW_MAX] = {};
+    // 16-byte dy loads need a 16-byte aligned pixel: run_engine also sends the NARROW_TLAST /
+    // NARROW_DIRECT plans here when dy is a misaligned channel slice
+    const bool dvec = (Co & 3) == 0 && (p.lda & 3) == 0 && (((uintptr_t)p.A) & 15) == 0;
     for (int a = 0; a < g.Th; ++a) {
         int i = ph.i0h + a * g.sh;
         int th = h + g.pt - i;
@@ -605,7 +608,7 @@ k_narrow_dgrad(const GemmArgs p, int w_in_lds) {
             if (wo >= g.Wo) continue;
             const float *dyp = p.A + ((long)(n * g.Ho + ho) * g.Wo + wo) * p.lda;
             const float *wp = wsrc + (long)(i * g.kw + j) * Ci * Co;
-            if ((Co & 3) == 0 && (p.lda & 3) == 0) {
+            if (dvec) {
                 for (int co = 0; co < Co; co += 4) {
                     f32x4 d = *reinterpret_cast<const f32x4 *>(dyp + co);
 #pragma unroll

@@ -100,8 +100,8 @@ def _cases(rows):
 
 
 # tests/test_conv_gpu.py CASES / HALO_CASES, tests/test_x3_gpu.py X3_CASES and its other layer
-# descriptors, tests/test_fused_pool_gpu.py (tests/test_boundary_gpu.py creates no conv
-# descriptor of its own: its steps run the pix2pix networks above)
+# descriptors, tests/test_fused_pool_gpu.py, tests/conv_variants.py CASES (tests/test_boundary_gpu.py
+# creates no conv descriptor of its own: its steps run the pix2pix networks above)
 TEST_CASES = [
     ("G.down1", 2, 64, 64, 3, 64, 4, 2, "same", False),
     ("G.down2", 2, 32, 32, 64, 128, 4, 2, "same", False),
@@ -146,10 +146,15 @@ TEST_CASES = [
     ("h32.splitk", 2, 8, 8, 256, 32, 3, 1, "same", False),
     ("h2.down", 2, 32, 32, 64, 128, 4, 2, "same", False),
     ("h2.up", 2, 16, 16, 256, 64, 4, 2, "same", True),
-    ("h2.ragged", 3, 26, 40, 32, 64, 4, 2, "same", False),
-    ("h2.odd", 2, 17, 15, 16, 32, 4, 2, "same", False),
-    ("h2.splitk", 2, 8, 8, 512, 512, 4, 2, "same", False),
-    ("h2.valid", 2, 20, 22, 32, 64, 4, 2, "valid", False),
+    ("h2.ragged", 1, 29, 61, 16, 32, 4, 2, "same", False),
+    ("h2.odd", 2, 13, 27, 16, 32, 4, 2, "same", False),
+    ("h2.splitk", 1, 13, 27, 32, 512, 4, 2, "same", False),
+    ("h2.valid", 2, 14, 28, 32, 64, 4, 2, "valid", False),
+    ("h2.tail", 2, 13, 27, 10, 32, 4, 2, "same", False),
+    ("g2.ragged", 3, 26, 40, 32, 64, 4, 2, "same", False),
+    ("g2.odd", 2, 17, 15, 16, 32, 4, 2, "same", False),
+    ("g2.splitk", 2, 8, 8, 512, 512, 4, 2, "same", False),
+    ("g2.valid", 2, 20, 22, 32, 64, 4, 2, "valid", False),
     ("h4.pad", 2, 18, 21, 32, 64, 4, 1, P1, False),
     ("h4.same", 3, 11, 17, 16, 32, 4, 1, "same", False),
     ("h4.bn128", 2, 16, 16, 64, 256, 4, 1, P1, False),
@@ -170,6 +175,22 @@ TEST_CASES = [
     ("pool.nos2", 8, 64, 64, 64, 128, 4, 2, "same", False),
     ("pool.b1c2like", 8, 64, 64, 64, 64, 3, 1, "same", False),
     ("pool.b5like", 16, 16, 16, 512, 512, 3, 1, "same", False),
+    # tests/conv_variants.py CASES (those not listed above)
+    ("v.gemm.tail", 2, 9, 7, 10, 32, 3, 1, "same", False),
+    ("v.gemm.k4s2", 2, 8, 8, 32, 32, 4, 2, "same", False),
+    ("v.halo3", 2, 9, 17, 32, 64, 3, 1, "same", False),
+    ("v.h2.up", 2, 7, 14, 64, 32, 4, 2, "same", True),
+    ("v.small.c3", 1, 8, 64, 3, 64, 4, 2, "same", False),
+    ("v.small.c6", 1, 8, 64, 6, 64, 4, 2, "same", False),
+    ("v.small.k3", 1, 4, 32, 3, 64, 3, 1, "same", False),
+    ("v.co1.s2", 2, 9, 11, 64, 1, 4, 2, "same", False),
+    ("v.narrow.px", 1, 64, 64, 64, 3, 1, 1, "same", False),
+    ("v.narrow.dgrad", 2, 9, 7, 4, 16, 3, 2, "same", False),
+    ("v.direct.c3", 2, 9, 13, 3, 64, 3, 1, "same", False),
+    ("v.direct.c6", 2, 10, 14, 6, 64, 4, 2, "same", False),
+    ("v.tlast", 1, 5, 9, 128, 3, 4, 2, "same", True),
+    ("v.recast.dgrad", 2, 5, 7, 160, 3, 4, 2, "same", True),
+    ("v.ntile", 2, 9, 11, 3, 32, 3, 1, "same", False),
 ]
 
 

@@ -9,6 +9,7 @@ three bf16 pieces, six piece products on the bf16 matrix cores).
 Tolerance vs fp64: relative L2 error < 2e-6 and max-abs error
 < 1e-5 * max|ref| (scaled by sqrt(K/1024) for long K)."""
 import math
+import re
 import zlib
 
 import pytest
@@ -144,10 +145,21 @@ HALO_CASES = [
     # differ in size, BN 64 / 128, split-K)
     ("h2.down", 2, 32, 32, 64, 128, 4, 2, "same", False, False),
     ("h2.up", 2, 16, 16, 256, 64, 4, 2, "same", True, False),
-    ("h2.ragged", 3, 26, 40, 32, 64, 4, 2, "same", False, True),
-    ("h2.odd", 2, 17, 15, 16, 32, 4, 2, "same", False, False),
-    ("h2.splitk", 2, 8, 8, 512, 512, 4, 2, "same", False, False),
-    ("h2.valid", 2, 20, 22, 32, 64, 4, 2, "valid", False, True),
+    # (the planner's 3/4-fill rule takes a phase grid that fills its 8 x 16 patches too thinly
+    # off the phase kernel: these shapes are the smallest that stay on it) a 15 x 31 phase grid
+    # on 8 x 16 patches, odd H and W (phases of 7/6 x 14/13), split-K over 16 chunk groups,
+    # 'valid' padding, and an input gradient of 10 columns (the epilogue's tail columns)
+    ("h2.ragged", 1, 29, 61, 16, 32, 4, 2, "same", False, True),
+    ("h2.odd", 2, 13, 27, 16, 32, 4, 2, "same", False, False),
+    ("h2.splitk", 1, 13, 27, 32, 512, 4, 2, "same", False, False),
+    ("h2.valid", 2, 14, 28, 32, 64, 4, 2, "valid", False, True),
+    ("h2.tail", 2, 13, 27, 10, 32, 4, 2, "same", False, False),
+    # stride-2 4x4 layers whose phase grids fill their patches below 3/4: the input gradient
+    # stays on the implicit-GEMM kernel in 4 phases (ragged tiles, odd sizes, 16 splits, 'valid')
+    ("g2.ragged", 3, 26, 40, 32, 64, 4, 2, "same", False, True),
+    ("g2.odd", 2, 17, 15, 16, 32, 4, 2, "same", False, False),
+    ("g2.splitk", 2, 8, 8, 512, 512, 4, 2, "same", False, False),
+    ("g2.valid", 2, 20, 22, 32, 64, 4, 2, "valid", False, True),
     # stride-1 4x4 (the PatchGAN's ZeroPadding2D + Conv2D(512, 4)): the input
     # gradient on the 11 x 19 halo, ragged patches, 'same' (asymmetric pads)
     ("h4.pad", 2, 18, 21, 32, 64, 4, 1, (1, 1, 1, 1), False, False),
@@ -156,15 +168,36 @@ HALO_CASES = [
 ]
 
 
+# the kernel each family of HALO_CASES must plan (DG_PLAN_DEBUG name), per engine mode: 0 FWD,
+# 1 DGRAD (the input gradient; a transposed layer's forward)
+HALO_KERNELS = {"h": {0: "x6h", 1: "x6h"}, "h32": {0: "x6h", 1: "x6h"}, "h2": {1: "x6h2"}, "g2": {1: "x6"},
+                "h4": {1: "x6h4"}}
+
+
+def halo_plan_kernels(err):
+    """{mode: kernel name} of the DG_PLAN_DEBUG lines (the last per mode: the bf16x6 plan)."""
+    out = {}
+    for line in err.splitlines():
+        m = re.match(r"\[dg plan\] mode (\d) .* -> (\S+) cfg", line)
+        if m:
+            out[int(m.group(1))] = m.group(2)
+    return out
+
+
 @gpu
 @pytest.mark.parametrize("case", HALO_CASES, ids=[c[0] for c in HALO_CASES])
-def test_conv_halo_kernel(case, monkeypatch):
+def test_conv_halo_kernel(case, monkeypatch, capfd):
     # force the bf16x6 path (the planner keeps small GEMMs on the fp32 kernel);
-    # every stride-1 3x3 bf16x6 FWD / DGRAD plan and every stride-2 4x4 DGRAD
-    # runs on the halo kernel
+    # every stride-1 3x3 bf16x6 FWD / DGRAD plan runs on the halo kernel, and the
+    # stride-2 / stride-1 4x4 DGRADs whose patches the planner finds full enough
     monkeypatch.setenv("DG_FORCE_X6CFG", "0")
     monkeypatch.delenv("DG_PLAN_DISABLE", raising=False)
+    monkeypatch.setenv("DG_PLAN_DEBUG", "1")
+    capfd.readouterr()
     test_conv_layer(case, "bf16x6")
+    kernels = halo_plan_kernels(capfd.readouterr().err)
+    for mode, name in HALO_KERNELS[case[0].split(".")[0]].items():
+        assert kernels.get(mode) == name, f"{case[0]}: mode {mode} planned {kernels.get(mode)}, expected {name}"
 
 
 @gpu
@@ -181,23 +214,26 @@ def test_conv_strided_views_and_accumulate(math_mode):
     w = torch.randn(*d.weight_shape, device=dev) * 0.05
     out = torch.randn(N, d.Ho, d.Wo, Cout + 128, device=dev)
     y = out[..., :Cout]
-    y0 = y.clone()
+    out0 = out.clone()
+    y0 = out0[..., :Cout]
     d.fwd(x, w, y, beta=1.0)
     ref = conv2d_ref(x.double().cpu(), w.double().cpu(), 2, d.pads) + y0.double().cpu()
     torch.cuda.synchronize()
     _close(y, ref, 16 * Cin, "strided fwd beta=1")
     # untouched channels stay intact
-    assert torch.equal(out[..., Cout:].cpu(), out[..., Cout:].cpu())
+    assert torch.equal(out[..., Cout:], out0[..., Cout:])
     # bwd_data into a slice, accumulate
     dy = torch.randn(N, d.Ho, d.Wo, Cout, device=dev)
     dxbuf = torch.randn(N, H, W, Cin + 32, device=dev)
     dx = dxbuf[..., 32:]
-    dx0 = dx.clone()
+    dxbuf0 = dxbuf.clone()
+    dx0 = dxbuf0[..., 32:]
     d.bwd_data(dy, w, dx, beta=1.0)
     xr = x.double().cpu().requires_grad_()
     conv2d_ref(xr, w.double().cpu(), 2, d.pads).backward(dy.double().cpu())
     torch.cuda.synchronize()
     _close(dx, xr.grad + dx0.double().cpu(), 16 * Cout, "strided bwd_data beta=1")
+    assert torch.equal(dxbuf[..., :32], dxbuf0[..., :32])
 
 
 @gpu
