@@ -159,6 +159,8 @@ _SIGS = {
     "dg_ssim_f32": (c_int, [c_int, c_int, c_int, c_int, _P, _P, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
     "dg_resize_u8": (c_int, [c_int] * 6 + [_P] * 6 + [c_double, c_double, _P]),
     "dg_resize_f32": (c_int, [c_int] * 6 + [_P] * 6 + [_P]),
+    "dg_jpeg_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
+    "dg_jpeg_roundtrip_u8": (c_int, [c_int] * 3 + [_P, _P, c_void_p, _P, c_size_t, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

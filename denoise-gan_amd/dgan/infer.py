@@ -376,6 +376,19 @@ class Denoiser:
             plan.forward(f.tin[t0:t0 + B], f.tout[t0:t0 + B])
         ops.u8_unstage(f.tout[:f.nt], f.u8_out, f.g)
 
+    def frame(self, n, h, w):
+        """The buffers of n images of h x w (made, and with graph=True captured, on first use)."""
+        return self._frame(n, h, w)
+
+    def run_frame(self, f):
+        """Denoise what the frame's `u8_in` holds into its `u8_out` on the current stream (a replay
+        of the captured graph where there is one); returns the frame."""
+        if f.graph is not None:
+            f.graph.replay()
+        else:
+            self._run(f)
+        return f
+
     def run(self, images):
         """Upload uint8 numpy images [n,h,w,3] (n >= 1) and denoise them on the current stream
         without reading anything back: the frame whose device buffers `u8_in` / `u8_out` hold the

@@ -10,7 +10,8 @@ and the host timings use them.  `psnr` / `ssim` run on the device (csrc/metrics.
 or fp32 NHWC tensors and return device fp64 tensors without a host synchronisation; `Evaluator`
 scores a `Denoiser`'s input and output frame against a clean frame where they already are, and
 `SREvaluator` an `Upscaler`'s output and the bicubic baseline (dgan/resize.py) against the
-high-resolution original.
+high-resolution original.  Both can degrade a clean frame themselves with the device JPEG round
+trip (dgan/jpeg.py), so a whole evaluation stays on the device.
 """
 import numpy as np
 
@@ -226,12 +227,37 @@ class Evaluator:
         f = self.denoiser.run(noisy)
         ref, res = self.buffers(tuple(noisy.shape))
         ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))
+        return self._score(f, ref, res)
+
+    def _score(self, f, ref, res):
         psnr(f.u8_in, ref, out=res[0])
         psnr(f.u8_out, ref, out=res[1])
         ssim(f.u8_in, ref, out=res[2])
         ssim(f.u8_out, ref, out=res[3])
         r = res.cpu().numpy()
         return {k: r[i] for i, k in enumerate(SCORES)}
+
+    def evaluate_degraded(self, clean_u8, jpeg_quality):
+        """uint8 [n,h,w,3] (or [h,w,3]) clean images -> the scores of `evaluate` with the noisy
+        images made here: the clean frame is uploaded once and its JPEG round trip at
+        `jpeg_quality` (dgan.jpeg, the degradation of dataloader.adjust_jpeg_quality) is written
+        into the Denoiser frame's `u8_in` on the device."""
+        import torch
+        from .jpeg import _check_quality, jpeg_roundtrip
+        clean = np.asarray(clean_u8)
+        if clean.ndim == 3:
+            clean = clean[None]
+        if clean.dtype != np.uint8 or clean.ndim != 4 or clean.shape[-1] != 3:
+            raise ValueError(f"evaluate_degraded expects uint8 [n,h,w,3] or [h,w,3], got {clean.dtype} {clean.shape}")
+        quality = _check_quality(jpeg_quality, "evaluate_degraded")
+        if clean.shape[0] == 0:
+            return {k: np.zeros(0) for k in SCORES}
+        f = self.denoiser.frame(*clean.shape[:3])
+        ref, res = self.buffers(tuple(clean.shape))
+        ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))
+        jpeg_roundtrip(ref, quality, out=f.u8_in)
+        self.denoiser.run_frame(f)
+        return self._score(f, ref, res)
 
 
 SR_SCORES = ("psnr_bicubic", "psnr_upscaled", "ssim_bicubic", "ssim_upscaled")
@@ -244,19 +270,24 @@ class SREvaluator:
     back (the display conversion) is the baseline; both are scored against the original and only
     the 4 n scalars come back.  `method` names the resize of both directions.  With a
     graph-capturing `Upscaler` the resizes and the metrics run eagerly around the replay.
-    jpeg_quality Q adds the one host step: the low-resolution frame comes back, goes through
-    Pillow's JPEG codec at quality Q with 4:2:0 subsampling (dataloader.jpeg_roundtrip on uint8)
-    and is uploaded again."""
+    jpeg_quality Q puts the low-resolution frame through a JPEG round trip at quality Q with 4:2:0
+    subsampling (dataloader.jpeg_roundtrip on uint8), in place: codec "device" on the device
+    (dgan.jpeg, the same bits), codec "pillow" on the host through Pillow's codec (a read-back, one
+    image at a time, and an upload)."""
 
     MAX_SHAPES = 4   # (original, baseline, scores) triples kept, least recently used first out
 
-    def __init__(self, upscaler, method="bicubic", jpeg_quality=None):
+    CODECS = ("device", "pillow")
+
+    def __init__(self, upscaler, method="bicubic", jpeg_quality=None, codec="device"):
         from .resize import METHODS
         if method not in METHODS:
             raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+        if codec not in self.CODECS:
+            raise ValueError(f"codec must be one of {self.CODECS}, got {codec!r}")
         if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
             raise ValueError(f"jpeg_quality must be in 1..100, got {jpeg_quality}")
-        self.upscaler, self.method = upscaler, method
+        self.upscaler, self.method, self.codec = upscaler, method, codec
         self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
         self._bufs = {}
 
@@ -271,7 +302,11 @@ class SREvaluator:
                              torch.empty((len(SR_SCORES), shape[0]), dtype=torch.float64, device=dev)), self.MAX_SHAPES)
 
     def _jpeg(self, low):
-        """The host step: every image of the device frame `low` through the JPEG codec, in place."""
+        """Every image of the device frame `low` through the JPEG round trip, in place."""
+        if self.codec == "device":
+            from .jpeg import jpeg_roundtrip
+            jpeg_roundtrip(low, self.jpeg_quality, out=low)
+            return
         import io
         import torch
         from PIL import Image

@@ -7,6 +7,7 @@ torch stream and never synchronises.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from ._lib import call, lib, DGError
@@ -1224,4 +1225,39 @@ def resize(x, out, iy, wy, ix, wx, mul=1.0, bias=0.0):
         if mul != 1.0 or bias != 0.0:
             raise DGError("resize: mul / bias apply to uint8 images only")
         call("dg_resize_f32", n, hi, wi, C, ho, wo, _p(x), _p(out), _p(iy), _p(wy), _p(ix), _p(wx), _stream())
+    return out
+
+
+# ---- JPEG round trip (include/dgan.h "JPEG round trip") -------------------------------------------
+def jpeg_workspace_bytes(n, h, w):
+    nb = ctypes.c_size_t()
+    call("dg_jpeg_ws_bytes", int(n), int(h), int(w), ctypes.byref(nb))
+    return nb.value
+
+
+def jpeg_roundtrip(x, out, qtab, ws):
+    """out[n,h,w,3] = the JPEG round trip (dg_jpeg_roundtrip_u8) of the dense uint8 images
+    x[n,h,w,3]; out may be x.  qtab: the host uint8 [2,64] tables of dgan.jpeg.quant_tables; ws: a
+    uint8 device buffer of jpeg_workspace_bytes."""
+    for t in (x, out):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise DGError(f"jpeg_roundtrip: expected uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 4 or not t.is_contiguous() or t.shape[3] != 3:
+            raise DGError(f"jpeg_roundtrip: expected dense [n,h,w,3] tensors, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise DGError("jpeg_roundtrip: expected device tensors (the HIP path has no CPU fallback)")
+    if out.shape != x.shape or out.device != x.device:
+        raise DGError(f"jpeg_roundtrip: the output {tuple(out.shape)} on {out.device} does not match the input "
+                      f"{tuple(x.shape)} on {x.device}")
+    q = np.asarray(qtab)
+    if q.dtype != np.uint8 or q.shape != (2, 64) or int(q.min()) < 1:
+        raise DGError(f"jpeg_roundtrip: qtab must be uint8 [2,64] with entries >= 1, got {q.dtype} {q.shape}")
+    n, h, w, _ = x.shape
+    need = jpeg_workspace_bytes(n, h, w)
+    if n and (not isinstance(ws, torch.Tensor) or ws.dtype != torch.uint8 or not ws.is_contiguous()
+              or ws.device != x.device or ws.numel() < need):
+        raise DGError(f"jpeg_roundtrip ws: expected a dense uint8 buffer of at least {need} bytes on {x.device}")
+    tables = (ctypes.c_ubyte * 128).from_buffer_copy(np.ascontiguousarray(q).tobytes())
+    call("dg_jpeg_roundtrip_u8", n, h, w, _p(x), _p(out), tables, _p(ws) if n else None, ws.numel() if n else 0,
+         _stream())
     return out

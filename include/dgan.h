@@ -679,6 +679,20 @@ int dg_resize_u8(int n, int hi, int wi, int C, int ho, int wo, const unsigned ch
 int dg_resize_f32(int n, int hi, int wi, int C, int ho, int wo, const float *in, float *out, const int *iy,
                   const double *wy, const int *ix, const double *wx, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * JPEG round trip (dgan/jpeg.py jpeg_ref: libjpeg's compress + decompress at 4:2:0 with the
+ * "islow" DCTs and "fancy" upsampling, minus the lossless entropy coder).  Dense RGB images
+ * [n][h][w][3] -> the same shape, any byte alignment; int32 arithmetic only, so the result equals
+ * jpeg_ref (and Pillow) bit for bit.  qtab: 128 HOST bytes, the luminance then the chrominance
+ * quantisation table, row-major, every entry >= 1; they travel to the kernels by value (no upload:
+ * the call can be captured in a graph).  Two launches: blocks (colour, downsample, DCT, quantise,
+ * dequantise, IDCT into uint8 Y / Cb / Cr planes in the workspace), then pixels (upsample, colour).
+ * `in` and `out` may be the same buffer.  dg_jpeg_ws_bytes: the workspace of one call (8-byte
+ * aligned); it is written in full and nothing beyond it. */
+int dg_jpeg_ws_bytes(int n, int h, int w, size_t *bytes);
+int dg_jpeg_roundtrip_u8(int n, int h, int w, const unsigned char *in, unsigned char *out, const unsigned char *qtab,
+                         void *ws, size_t ws_bytes, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
