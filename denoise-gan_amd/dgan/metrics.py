@@ -187,28 +187,54 @@ def ssim(a, b, max_val=None, scale=1.0, shift=0.0, out=None):
 
 
 SCORES = ("psnr_noisy", "psnr_denoised", "ssim_noisy", "ssim_denoised")
+BASELINE_SCORES = ("psnr_baseline", "ssim_baseline")
+BASELINES = ("median3", "nlm")
 
 
 class Evaluator:
     """Scores a `Denoiser`'s frames against clean frames on the device: the noisy input and the
     denoised output stay where `Denoiser` holds them (uint8, dense), the clean frame is uploaded
     beside them, and only the 4 n scalars come back.  With a graph-capturing `Denoiser` the metrics
-    run eagerly on the same stream after the replay."""
+    run eagerly on the same stream after the replay.  baseline "median3" or "nlm" (baseline_args:
+    the keywords of dgan.filters.nlm, h / template / search) also puts the noisy input through
+    that classical filter on the device and scores it the same way: `psnr_baseline` and
+    `ssim_baseline` join the result, 6 n scalars in all."""
 
     MAX_SHAPES = 4   # (clean frame, scores) pairs kept, least recently used first out
 
-    def __init__(self, denoiser):
-        self.denoiser = denoiser
+    def __init__(self, denoiser, baseline=None, baseline_args=None):
+        from . import filters
+        if baseline is not None and baseline not in BASELINES:
+            raise ValueError(f"baseline must be None or one of {BASELINES}, got {baseline!r}")
+        args = dict(baseline_args or {})
+        if args and baseline != "nlm":
+            raise ValueError(f"baseline_args apply to the baseline 'nlm' only, got {sorted(args)} with {baseline!r}")
+        if set(args) - {"h", "template", "search"}:
+            raise ValueError(f"baseline_args: unknown keys {sorted(set(args) - {'h', 'template', 'search'})}")
+        if baseline == "nlm":
+            args = dict(zip(("h", "template", "search"), filters.check_nlm(
+                args.get("h", 10), args.get("template", 7), args.get("search", 21), "baseline_args")))
+        self.denoiser, self.baseline, self.baseline_args = denoiser, baseline, args
+        self.scores = SCORES + (BASELINE_SCORES if baseline else ())
         self._bufs = {}
 
     def buffers(self, shape):
         """(the device uint8 clean frame, the device fp64 scores [4, n] in SCORES order) of one
-        image shape (n, h, w, 3): what the last `evaluate` of that shape left."""
+        image shape (n, h, w, 3): what the last `evaluate` of that shape left.  With a baseline the
+        scores are [6, n] (SCORES, then BASELINE_SCORES)."""
         import torch
         dev = self.denoiser.device
         return _lru(self._bufs, tuple(shape),
                     lambda: (torch.empty(shape, dtype=torch.uint8, device=dev),
-                             torch.empty((len(SCORES), shape[0]), dtype=torch.float64, device=dev)), self.MAX_SHAPES)
+                             torch.empty((len(self.scores), shape[0]), dtype=torch.float64, device=dev)),
+                    self.MAX_SHAPES)
+
+    def filtered(self, f):
+        """The frame's noisy input through the baseline filter: the filter's own buffer of that shape."""
+        from . import filters
+        if self.baseline == "median3":
+            return filters.median3(f.u8_in)
+        return filters.nlm(f.u8_in, **self.baseline_args)
 
     def evaluate(self, noisy_u8, clean_u8):
         """uint8 [n,h,w,3] (or [h,w,3]) noisy and clean images -> {"psnr_noisy", "psnr_denoised",
@@ -223,7 +249,7 @@ class Evaluator:
         if noisy.dtype != np.uint8 or noisy.ndim != 4 or noisy.shape[-1] != 3:
             raise ValueError(f"evaluate expects uint8 [n,h,w,3] or [h,w,3], got {noisy.dtype} {noisy.shape}")
         if noisy.shape[0] == 0:
-            return {k: np.zeros(0) for k in SCORES}
+            return {k: np.zeros(0) for k in self.scores}
         f = self.denoiser.run(noisy)
         ref, res = self.buffers(tuple(noisy.shape))
         ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))
@@ -234,8 +260,12 @@ class Evaluator:
         psnr(f.u8_out, ref, out=res[1])
         ssim(f.u8_in, ref, out=res[2])
         ssim(f.u8_out, ref, out=res[3])
+        if self.baseline:
+            base = self.filtered(f)
+            psnr(base, ref, out=res[4])
+            ssim(base, ref, out=res[5])
         r = res.cpu().numpy()
-        return {k: r[i] for i, k in enumerate(SCORES)}
+        return {k: r[i] for i, k in enumerate(self.scores)}
 
     def evaluate_degraded(self, clean_u8, jpeg_quality):
         """uint8 [n,h,w,3] (or [h,w,3]) clean images -> the scores of `evaluate` with the noisy
@@ -251,7 +281,7 @@ class Evaluator:
             raise ValueError(f"evaluate_degraded expects uint8 [n,h,w,3] or [h,w,3], got {clean.dtype} {clean.shape}")
         quality = _check_quality(jpeg_quality, "evaluate_degraded")
         if clean.shape[0] == 0:
-            return {k: np.zeros(0) for k in SCORES}
+            return {k: np.zeros(0) for k in self.scores}
         f = self.denoiser.frame(*clean.shape[:3])
         ref, res = self.buffers(tuple(clean.shape))
         ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))

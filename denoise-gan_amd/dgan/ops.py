@@ -1261,3 +1261,40 @@ def jpeg_roundtrip(x, out, qtab, ws):
     call("dg_jpeg_roundtrip_u8", n, h, w, _p(x), _p(out), tables, _p(ws) if n else None, ws.numel() if n else 0,
          _stream())
     return out
+
+
+# ---- classical filters (include/dgan.h "Classical filters") -------------------------------------
+def _filter_pair(x, out, what):
+    for t in (x, out):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise DGError(f"{what}: expected uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 4 or not t.is_contiguous() or t.shape[3] != 3:
+            raise DGError(f"{what}: expected dense [n,h,w,3] tensors, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise DGError(f"{what}: expected device tensors (the HIP path has no CPU fallback)")
+    if out.shape != x.shape or out.device != x.device:
+        raise DGError(f"{what}: the output {tuple(out.shape)} on {out.device} does not match the input "
+                      f"{tuple(x.shape)} on {x.device}")
+    if x.numel() and out.data_ptr() == x.data_ptr():
+        raise DGError(f"{what}: the output must not be the input")
+    return x.shape[:3]
+
+
+def median3(x, out):
+    """out[n,h,w,3] = the 3x3 median per channel, edges replicated (dg_median3_u8), of the dense
+    uint8 images x[n,h,w,3]; out must not be x."""
+    n, h, w = _filter_pair(x, out, "median3")
+    call("dg_median3_u8", n, h, w, _p(x), _p(out), _stream())
+    return out
+
+
+def nlm(x, out, table, template, search):
+    """out[n,h,w,3] = joint-RGB non-local means (dg_nlm_u8) of the dense uint8 images x[n,h,w,3];
+    out must not be x.  table: the device int16 weights of dgan.filters.nlm_table (table[0] >= 1,
+    no entry above 2^14)."""
+    n, h, w = _filter_pair(x, out, "nlm")
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int16 or table.dim() != 1
+            or not table.is_contiguous() or table.device != x.device or table.numel() < 1):
+        raise DGError(f"nlm table: expected a dense int16 vector on {x.device}")
+    call("dg_nlm_u8", n, h, w, int(template), int(search), _p(table), table.numel(), _p(x), _p(out), _stream())
+    return out

@@ -3,6 +3,7 @@ and after the trained pix2pix generator.
 
     python evaluate.py --image_dir noisy/ --target_dir clean/ --model models/pix2pix.npz --json scores.json
     python evaluate.py --jpeg_quality 50 --target_dir clean/ --model models/pix2pix.npz --json scores.json
+    python evaluate.py --image_dir noisy/ --target_dir clean/ --model models/pix2pix.npz --baseline nlm
 
 Files pair by stem (noisy/a.png with clean/a.jpg); a file without a partner, a pair of different
 sizes, or an image smaller than the 11x11 SSIM window is refused by name.  With --model every
@@ -15,6 +16,9 @@ the two directories are compared directly: psnr, ssim.  With --jpeg_quality Q in
 quality Q with 4:2:0 subsampling on the device (dgan.jpeg, the degradation the training pipeline
 applies, bit for bit what Pillow's codec returns), and the scores are the same.  The metrics are
 the tf.image.psnr / tf.image.ssim defaults on uint8 RGB (max_val 255), accumulated in fp64.
+--baseline median3 | nlm also puts every noisy image through that classical filter on the device
+(dgan.filters; --nlm_h / --nlm_template / --nlm_search) and scores the result the same way:
+psnr_baseline, ssim_baseline, with and without --model.
 """
 import json
 import os
@@ -37,6 +41,11 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
+parser.add_argument("--baseline", default=None, choices=["median3", "nlm"],
+                    help="Also score a classical filter of the noisy image: the 3x3 median or non-local means.")
+parser.add_argument("--nlm_h", default=10, type=int, help="Non-local means: the filter strength (1..40).")
+parser.add_argument("--nlm_template", default=7, type=int, help="Non-local means: the patch size (3, 5 or 7).")
+parser.add_argument("--nlm_search", default=21, type=int, help="Non-local means: the search window (odd, 3..21).")
 parser.add_argument("--json", default=None, type=str, help="Also write the scores and their means to this file.")
 
 
@@ -66,6 +75,18 @@ def _read_rgb(path):
         return np.asarray(im.convert("RGB"), np.uint8)
 
 
+def baseline_args(args):
+    """The keywords of dgan.filters.nlm that --baseline nlm asks for ({} for the other baselines).
+    ValueError naming a bad --nlm_* value, or one given without --baseline nlm."""
+    from dgan.filters import check_nlm
+    given = (args.nlm_h, args.nlm_template, args.nlm_search)
+    if args.baseline != "nlm":
+        if given != (10, 7, 21):
+            raise ValueError("--nlm_h / --nlm_template / --nlm_search need --baseline nlm")
+        return {}
+    return dict(zip(("h", "template", "search"), check_nlm(*given, what="--baseline nlm")))
+
+
 def summarize(rows):
     """{"images": rows, "mean": the mean of each score over the images}."""
     keys = [k for k in (rows[0] if rows else {}) if k != "name"]
@@ -74,9 +95,13 @@ def summarize(rows):
 
 def main(argv=None):
     import torch
-    from dgan import metrics
+    from dgan import filters, metrics
     from dgan.jpeg import jpeg_roundtrip
     args = parser.parse_args(argv)
+    try:
+        nlm_args = baseline_args(args)
+    except ValueError as e:
+        parser.error(str(e))
     if (args.image_dir is None) == (args.jpeg_quality is None):
         parser.error("give exactly one of --image_dir and --jpeg_quality")
     if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
@@ -97,7 +122,8 @@ def main(argv=None):
         from infer import load_generator
         model_path = os.path.expanduser(os.path.expandvars(args.model))
         evaluator = metrics.Evaluator(Denoiser(load_generator(model_path), tile=args.tile or None, margin=args.margin,
-                                               pad=args.pad, batch=args.batch))
+                                               pad=args.pad, batch=args.batch),
+                                      baseline=args.baseline, baseline_args=nlm_args)
     rows = []
     for stem, image_name, target_name in pairs:
         clean = _read_rgb(os.path.join(target_dir, target_name))
@@ -111,11 +137,14 @@ def main(argv=None):
         if evaluator is not None:
             r = evaluator.evaluate(noisy, clean) if image_dir is not None else evaluator.evaluate_degraded(
                 clean, args.jpeg_quality)
-            row = {k: float(r[k][0]) for k in metrics.SCORES}
+            row = {k: float(r[k][0]) for k in evaluator.scores}
         else:
             b = torch.from_numpy(clean[None]).cuda()
             a = torch.from_numpy(noisy[None]).cuda() if image_dir is not None else jpeg_roundtrip(b, args.jpeg_quality)
             row = {"psnr": float(metrics.psnr(a, b).item()), "ssim": float(metrics.ssim(a, b).item())}
+            if args.baseline:
+                c = filters.median3(a) if args.baseline == "median3" else filters.nlm(a, **nlm_args)
+                row.update(psnr_baseline=float(metrics.psnr(c, b).item()), ssim_baseline=float(metrics.ssim(c, b).item()))
         rows.append({"name": image_name, **row})
         print(image_name + "".join(f" {k} {v:.4f}" for k, v in row.items()))
     result = summarize(rows)

@@ -7,6 +7,8 @@ infer.py:24-83, without its display window).
 that names the width.  Images are read and written with Pillow, as RGB; each keeps its size and
 file name.  Whole images are padded to a multiple of 256 by default; --tile T (a multiple of 256)
 with --margin M runs T x T tiles with M pixels of context instead, --batch of them per forward.
+--post median3 puts the denoised frame through a 3x3 median on the device before it is read back
+(dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).
 
 Deviation from the reference: the generator is fed [-1, 1] (uint8 / 255 * 2 - 1, what it was
 trained on, dataloader.py:173-175); the reference's infer.py:55 feeds [0, 1].
@@ -25,6 +27,8 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
+parser.add_argument("--post", default=None, choices=["median3"],
+                    help="A classical filter applied to the denoised image on the device (default: none).")
 
 
 def load_generator(model_path):
@@ -53,7 +57,11 @@ def main(argv=None):
     for image_path in image_paths:
         with Image.open(image_path) as im:
             noisy = np.asarray(im.convert("RGB"), np.uint8)
-        clean = denoiser.denoise(noisy)
+        if args.post == "median3":
+            from dgan.filters import median3
+            clean = median3(denoiser.run(noisy[None]).u8_out).cpu().numpy()[0]
+        else:
+            clean = denoiser.denoise(noisy)
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(clean, "RGB").save(out_path)
         print(f"{image_path} -> {out_path} {clean.shape[1]}x{clean.shape[0]}")

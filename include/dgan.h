@@ -693,6 +693,24 @@ int dg_jpeg_ws_bytes(int n, int h, int w, size_t *bytes);
 int dg_jpeg_roundtrip_u8(int n, int h, int w, const unsigned char *in, unsigned char *out, const unsigned char *qtab,
                          void *ws, size_t ws_bytes, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * Classical filters (dgan/filters.py median3_ref / nlm_ref).  Dense RGB images [n][h][w][3] ->
+ * the same shape, any byte alignment; integer arithmetic only, so the results equal the numpy
+ * references bit for bit and two calls give the same bits.  One launch each, no workspace; `out`
+ * must not be `in`.
+ * dg_median3_u8: every channel's median over its 3x3 neighbourhood, edges replicated.
+ * dg_nlm_u8: joint-RGB non-local means with a t x t patch (t 3, 5 or 7) and an s x s search window
+ * (s odd, 3..21), the image reflected (np.pad "reflect") by t/2 + s/2:
+ *   D(p,d) = sum over the patch and the channels of (P(p+q) - P(p+d+q))^2,
+ *   w(p,d) = table[min(D / (3 t^2), table_len - 1)],
+ *   out(p,c) = (sum_d w P(p+d,c) + S / 2) / S,  S = sum_d w.
+ * table: table_len DEVICE uint16 weights (filters.nlm_table: floor(2^14 exp(-i / h^2) + 0.5), cut
+ * after its first 0), at most 18000 of them.  The caller guarantees table[0] >= 1 (S > 0) and no
+ * entry above 2^14 (the int32 sums hold 441 * 2^14 * 255); device memory is not checked here. */
+int dg_median3_u8(int n, int h, int w, const unsigned char *in, unsigned char *out, dg_stream_t stream);
+int dg_nlm_u8(int n, int h, int w, int t, int s, const unsigned short *table, int table_len, const unsigned char *in,
+              unsigned char *out, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
