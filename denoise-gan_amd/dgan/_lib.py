@@ -161,6 +161,11 @@ _SIGS = {
     "dg_resize_f32": (c_int, [c_int] * 6 + [_P] * 6 + [_P]),
     "dg_jpeg_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
     "dg_jpeg_roundtrip_u8": (c_int, [c_int] * 3 + [_P, _P, c_void_p, _P, c_size_t, _P]),
+    "dg_jpeg_encode_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
+    "dg_jpeg_encode_scan": (c_int, [c_int] * 3 + [_P, c_void_p, _P, c_size_t, _P, _P]),
+    "dg_jpeg_encode_out_bytes": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "dg_jpeg_encode_emit": (c_int, [c_int] * 3 + [_P, c_size_t, _P, c_int64, c_void_p, c_int, _P, c_size_t, _P, c_size_t,
+                                    _P, _P]),
     "dg_median3_u8": (c_int, [c_int] * 3 + [_P, _P, _P]),
     "dg_nlm_u8": (c_int, [c_int] * 5 + [_P, c_int, _P, _P, _P]),
 }

@@ -29,6 +29,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + INCLUDE, "-I" + CSRC,
             "-Wno-unused-result"]
+# further flags of single sources; jpeg_enc.hip: integer code, built without packed fp32 instructions
+EXTRA_FLAGS = {"jpeg_enc.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():
@@ -74,7 +76,8 @@ def build(verbose=False, jobs=None):
     sha = source_sha()
     # the library's own stamp: every source and the flags it was built from (the GPU box gets the
     # library and this stamp with the snapshot, not the objects: a current library is not rebuilt)
-    lib_digest = _digest([os.path.join(CSRC, f) for f in _sources()] + deps, CXXFLAGS + [ARCH, sha])
+    lib_digest = _digest([os.path.join(CSRC, f) for f in _sources()] + deps,
+                         CXXFLAGS + [ARCH, sha] + [f"{k}:{' '.join(v)}" for k, v in sorted(EXTRA_FLAGS.items())])
     if _stamp_ok(LIB_PATH, lib_digest):
         return LIB_PATH
     os.makedirs(OBJDIR, exist_ok=True)
@@ -83,7 +86,8 @@ def build(verbose=False, jobs=None):
     for f in _sources():
         src = os.path.join(CSRC, f)
         obj = os.path.join(OBJDIR, f[:-4] + ".o")
-        flags = CXXFLAGS + ([f'-DDG_SOURCE_SHA="{sha}"'] if f == "runtime.hip" else [])
+        flags = CXXFLAGS + EXTRA_FLAGS.get(f, [])
+        flags = flags + ([f'-DDG_SOURCE_SHA="{sha}"'] if f == "runtime.hip" else [])
         digest = _digest([src] + deps, flags)
         objs.append(obj)
         if not _stamp_ok(obj, digest):

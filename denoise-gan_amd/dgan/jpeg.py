@@ -31,7 +31,11 @@ Everything fits 32-bit integers at 8-bit samples (the device kernels use them; `
 working type as an argument and tests/test_jpeg.py holds the two equal), so the device output
 equals `jpeg_ref` bit for bit, and `jpeg_ref` equals Pillow.
 
-`quant_tables` / `jpeg_ref` are pure numpy and import neither torch nor the library.
+The encoder finishes the codec: `jpeg_encode_ref` Huffman-codes the same quantised levels into the
+baseline file Pillow writes (header, scan order, dummy blocks and coding rules: DESIGN.md section JPEG
+encoder), and `jpeg_encode` is the device op (csrc/jpeg_enc.hip), equal to it byte for byte.
+
+`quant_tables`, `jpeg_ref` and `jpeg_encode_ref` are pure numpy and import neither torch nor the library.
 """
 import numpy as np
 
@@ -110,13 +114,19 @@ def _along(f, x, axis, first):
     return np.stack(f([np.take(x, k, axis=axis) for k in range(8)], first), axis=axis)
 
 
+def _quantise(plane, table):
+    """A plane [n,H,W] (H, W multiples of 8) -> its quantised levels [n,by,bx,row,col]."""
+    n, H, W = plane.shape
+    b = (plane - 128).reshape(n, H // 8, 8, W // 8, 8).transpose(0, 1, 3, 2, 4)
+    c = _along(_fdct_1d, _along(_fdct_1d, b, 4, True), 3, False)
+    t = table.astype(plane.dtype).reshape(8, 8)
+    return np.sign(c) * ((np.abs(c) + 4 * t) // (8 * t))
+
+
 def _codec(plane, table):
     """A plane [n,H,W] (H, W multiples of 8) through the block pipeline with the table [64]."""
     n, H, W = plane.shape
-    b = (plane - 128).reshape(n, H // 8, 8, W // 8, 8).transpose(0, 1, 3, 2, 4)   # [n,by,bx,row,col]
-    c = _along(_fdct_1d, _along(_fdct_1d, b, 4, True), 3, False)
-    t = table.astype(plane.dtype).reshape(8, 8)
-    c = np.sign(c) * ((np.abs(c) + 4 * t) // (8 * t)) * t
+    c = _quantise(plane, table) * table.astype(plane.dtype).reshape(8, 8)
     x = _along(_idct_1d, _along(_idct_1d, c, 3, True), 4, False) & 1023
     x = np.where(x < 128, x + 128, np.where(x < 512, 255, np.where(x < 896, 0, x - 896)))
     return x.transpose(0, 1, 3, 2, 4).reshape(n, H, W)
@@ -145,6 +155,24 @@ def _upsample(c, fancy):
     return out
 
 
+def _planes(a, dtype):
+    """uint8 [n,h,w,3] -> what the block pipeline codes: Y [n,up8(h),up8(w)] and the downsampled
+    Cb and Cr [n,up8(ch),up8(cw)], edge-replicated (module docstring: colour, luma, chroma)."""
+    n, h, w = a.shape[:3]
+    ch, cw = -(-h // 2), -(-w // 2)
+    R, G, B = (a[..., k].astype(dtype) for k in range(3))
+    Y = (_fix(.299) * R + _fix(.587) * G + _fix(.114) * B + 32768) >> 16
+    Cb = (-_fix(.16874) * R - _fix(.33126) * G + _fix(.5) * B + (128 << 16) + 32767) >> 16
+    Cr = (_fix(.5) * R - _fix(.41869) * G - _fix(.08131) * B + (128 << 16) + 32767) >> 16
+    bias = np.where(np.arange(_up8(cw)) % 2 == 0, 1, 2).astype(dtype)
+    chroma = []
+    for C in (Cb, Cr):
+        C = _edge(C, 2 * ch, 2 * _up8(cw))
+        C = (C[:, 0::2, 0::2] + C[:, 0::2, 1::2] + C[:, 1::2, 0::2] + C[:, 1::2, 1::2] + bias) >> 2
+        chroma.append(_edge(C, _up8(ch), _up8(cw)))
+    return _edge(Y, _up8(h), _up8(w)), chroma[0], chroma[1]
+
+
 def jpeg_ref(img_u8, quality, dtype=np.int64):
     """The definition on the host: uint8 [n,h,w,3] or [h,w,3] -> the same shape and dtype (module
     docstring).  dtype: the working integer type, np.int64 or np.int32."""
@@ -161,17 +189,11 @@ def jpeg_ref(img_u8, quality, dtype=np.int64):
         a = a[None]
     n, h, w = a.shape[:3]
     ch, cw = -(-h // 2), -(-w // 2)
-    R, G, B = (a[..., k].astype(dtype) for k in range(3))
-    Y = (_fix(.299) * R + _fix(.587) * G + _fix(.114) * B + 32768) >> 16
-    Cb = (-_fix(.16874) * R - _fix(.33126) * G + _fix(.5) * B + (128 << 16) + 32767) >> 16
-    Cr = (_fix(.5) * R - _fix(.41869) * G - _fix(.08131) * B + (128 << 16) + 32767) >> 16
-    Y = _codec(_edge(Y, _up8(h), _up8(w)), tables[0])[:, :h, :w]
-    bias = np.where(np.arange(_up8(cw)) % 2 == 0, 1, 2).astype(dtype)
+    Y, Cb, Cr = _planes(a, dtype)
+    Y = _codec(Y, tables[0])[:, :h, :w]
     chroma = []
     for C in (Cb, Cr):
-        C = _edge(C, 2 * ch, 2 * _up8(cw))
-        C = (C[:, 0::2, 0::2] + C[:, 0::2, 1::2] + C[:, 1::2, 0::2] + C[:, 1::2, 1::2] + bias) >> 2
-        C = _codec(_edge(C, _up8(ch), _up8(cw)), tables[1])[:, :ch, :cw]
+        C = _codec(C, tables[1])[:, :ch, :cw]
         chroma.append(_upsample(C, cw > 2)[:, :h, :w] - 128)
     Cb, Cr = chroma
     out = np.stack([Y + ((_fix(1.402) * Cr + 32768) >> 16),
@@ -179,6 +201,175 @@ def jpeg_ref(img_u8, quality, dtype=np.int64):
                     Y + ((_fix(1.772) * Cb + 32768) >> 16)], axis=-1)
     out = np.clip(out, 0, 255).astype(np.uint8)
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
+# the baseline encoder: header, scan order, Huffman coding (module docstring of csrc/jpeg_enc.hip)
+# ---------------------------------------------------------------------------
+# ZIGZAG[k] = the row-major index of the k-th coefficient of a block in a file
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
+          21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53,
+          60, 61, 54, 47, 55, 62, 63)
+# Annex K.3 - K.6 as (codes per length 1..16, symbols in code order): DC0, AC0, DC1, AC1
+_AC_SYMBOLS = (0x00, 0xf0) + tuple(16 * r + s for r in range(16) for s in range(1, 11))   # EOB, ZRL, (run, size)
+HUFFMAN = (
+    ((0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), tuple(range(12))),
+    ((0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d),
+     (0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
+      0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
+      0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
+      0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59,
+      0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83,
+      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
+      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+      0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)),
+    ((0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), tuple(range(12))),
+    ((0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77),
+     (0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
+      0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+      0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
+      0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58,
+      0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a,
+      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
+      0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+      0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa)))
+assert all(sum(b) == len(v) and sorted(v) == sorted(set(v)) for b, v in HUFFMAN)
+assert all(sorted(HUFFMAN[k][1]) == sorted(_AC_SYMBOLS) for k in (1, 3))
+
+
+def huffman_codes(k):
+    """int64 [256]: HUFFMAN[k]'s code of every symbol packed (length << 16) | code, 0 where the
+    table has none (Annex C: codes count up within a length, doubled at every longer one)."""
+    bits, vals = HUFFMAN[k]
+    out, code, i = np.zeros(256, np.int64), 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            out[vals[i]] = (length << 16) | code
+            code, i = code + 1, i + 1
+        code <<= 1
+    return out
+
+
+def _segment(marker, payload):
+    return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + bytes(payload)
+
+
+def jpeg_header(h, w, quality):
+    """The bytes of a baseline 4:2:0 file of an h x w image from SOI to the end of SOS, as libjpeg
+    writes them by default: JFIF 1.01 without density, two 8-bit DQT, SOF0, four DHT, SOS."""
+    if not (1 <= int(h) <= 65535 and 1 <= int(w) <= 65535):
+        raise ValueError(f"jpeg_header: a JPEG file holds 1..65535 rows and columns, got {h}x{w}")
+    tables = quant_tables(_check_quality(quality, "jpeg_header"))
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\0\x01\x01\0\0\x01\0\x01\0\0")
+    for k in (0, 1):
+        out += _segment(0xDB, bytes([k]) + bytes(tables[k][list(ZIGZAG)]))
+    out += _segment(0xC0, bytes([8]) + int(h).to_bytes(2, "big") + int(w).to_bytes(2, "big") +
+                    bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for k, ident in enumerate((0x00, 0x10, 0x01, 0x11)):
+        out += _segment(0xC4, bytes([ident]) + bytes(HUFFMAN[k][0]) + bytes(HUFFMAN[k][1]))
+    return out + _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3F, 0]))
+
+
+def scan_coefficients(img_u8, quality):
+    """One uint8 [h,w,3] image -> int64 [mcu,6,64]: the quantised coefficients of the scan, MCUs
+    row-major over ceil(h/16) x ceil(w/16), blocks Y(0,0) Y(0,1) Y(1,0) Y(1,1) Cb Cr, each in zigzag
+    order.  A luma block outside the plane of multiples of 8 is libjpeg's dummy block: no AC, the
+    DC of the block before it in its MCU."""
+    a = np.asarray(img_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3:
+        raise ValueError(f"scan_coefficients: expected uint8 [h,w,3], got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    if not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"scan_coefficients: a JPEG file holds 1..65535 rows and columns, got {h}x{w}")
+    tables = quant_tables(_check_quality(quality, "scan_coefficients"))
+    Y, Cb, Cr = _planes(a[None], np.int64)
+    zz = list(ZIGZAG)
+    qy = _quantise(Y, tables[0])[0].reshape(Y.shape[1] // 8, Y.shape[2] // 8, 64)[..., zz]
+    my, mx = -(-h // 16), -(-w // 16)
+    out = np.zeros((my, mx, 6, 64), np.int64)
+    for k, C in enumerate((Cb, Cr)):
+        out[:, :, 4 + k] = _quantise(C, tables[1])[0].reshape(my, mx, 64)[..., zz]
+    for i in range(4):
+        sub = qy[i // 2::2, i % 2::2]
+        out[:sub.shape[0], :sub.shape[1], i] = sub
+        if i:   # the blocks this left empty, below or right of the plane: dummies
+            real = np.zeros((my, mx), bool)
+            real[:sub.shape[0], :sub.shape[1]] = True
+            out[..., i, 0] = np.where(real, out[..., i, 0], out[..., i - 1, 0])
+    return out.reshape(my * mx, 6, 64)
+
+
+def _bit_length(a):
+    s = np.zeros(a.shape, np.int64)
+    for k in range(16):
+        s += (a >> k) > 0
+    return s
+
+
+def scan_entries(coef):
+    """scan_coefficients' [mcu,6,64] -> what every coefficient puts into the bit stream, a dict of
+    int64 arrays.  "coef" [mcu,6,64]: the coefficients, DC as the difference to the block before of
+    its component.  [mcu,6,65] each, entry 64 the block's EOB: "symbol" the (run & 15, size) byte, the
+    size category at entry 0, -1 where nothing is coded; "zrl" the ZRL codes in front; "length"
+    the bits (0: nothing) and "value" those bits, the first highest: ZRL codes, Huffman code,
+    magnitude."""
+    v = np.array(coef, np.int64)
+    # DC: the difference to the block before of the same component, 0 before the first
+    v[:, :4, 0] = np.diff(v[:, :4, 0].reshape(-1), prepend=0).reshape(-1, 4)
+    v[:, 4:, 0] = np.diff(v[:, 4:, 0], axis=0, prepend=0)
+    size = _bit_length(np.abs(v))
+    mag = np.where(v < 0, v + (1 << size) - 1, v)
+    k = np.arange(64)
+    coded = v != 0
+    coded[..., 0] = True
+    last = np.maximum.accumulate(np.where(coded, k, 0), axis=-1)
+    run = k - 1 - np.concatenate([np.zeros_like(last[..., :1]), last[..., :-1]], axis=-1)
+    sym = np.where(coded, ((run & 15) << 4) | size, -1)
+    sym[..., 0] = size[..., 0]
+    sym = np.concatenate([sym, np.where(v[..., 63:] == 0, 0, -1)], axis=-1)
+    val, length, zrls = (np.zeros(sym.shape, np.int64) for _ in range(3))
+    for blocks, kdc, kac in ((slice(0, 4), 0, 1), (slice(4, 6), 2, 3)):
+        codes = np.stack([huffman_codes(kdc), huffman_codes(kac)])
+        which = np.ones(65, np.int64)
+        which[0] = 0
+        s = sym[:, blocks]
+        c = np.where(s >= 0, codes[which, np.maximum(s, 0)], 0)
+        assert np.all((c > 0) == (s >= 0)), "a symbol without a code"
+        zrl = np.zeros(s.shape, np.int64)
+        zrl[..., 1:64] = np.where(coded[:, blocks, 1:], run[:, blocks, 1:] >> 4, 0)
+        zc, zl = int(codes[1, 0xF0]) & 0xFFFF, int(codes[1, 0xF0]) >> 16
+        head = np.zeros(s.shape, np.int64)
+        for r in range(3):
+            head = np.where(zrl > r, (head << zl) | zc, head)
+        sz = np.concatenate([size[:, blocks], np.zeros_like(size[:, blocks, :1])], axis=-1) * (s >= 0)
+        mg = np.concatenate([mag[:, blocks], np.zeros_like(mag[:, blocks, :1])], axis=-1) * (s >= 0)
+        val[:, blocks] = (((head << (c >> 16)) | (c & 0xFFFF)) << sz) | mg
+        length[:, blocks] = zrl * zl + (c >> 16) + sz
+        zrls[:, blocks] = zrl
+    return {"coef": v, "symbol": sym, "zrl": zrls, "value": val, "length": length}
+
+
+def jpeg_encode_ref(img_u8, quality):
+    """The encoder's definition on the host: one uint8 [h,w,3] image -> the bytes of the baseline
+    JPEG file Pillow writes for `quality=quality, subsampling=2` with its defaults (Annex K Huffman
+    tables, no optimisation, no progressive mode, no restart markers)."""
+    quality = _check_quality(quality, "jpeg_encode_ref")
+    a = np.asarray(img_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[-1] != 3:
+        raise ValueError(f"jpeg_encode_ref: expected uint8 [h,w,3], got {a.dtype} {a.shape}")
+    if min(a.shape[:2]) < 1:
+        raise ValueError(f"jpeg_encode_ref: empty image: {a.shape}")
+    header = jpeg_header(a.shape[0], a.shape[1], quality)
+    e = scan_entries(scan_coefficients(a, quality))
+    val, length = e["value"].reshape(-1), e["length"].reshape(-1)
+    val, length = val[length > 0], length[length > 0]
+    owner = np.repeat(np.arange(length.size), length)
+    j = np.arange(owner.size) - np.repeat(np.cumsum(length) - length, length)   # 0: an entry's first bit
+    bits = ((val[owner] >> (length[owner] - 1 - j)) & 1).astype(np.uint8)
+    bits = np.concatenate([bits, np.ones(-bits.size % 8, np.uint8)])
+    return header + np.packbits(bits).tobytes().replace(b"\xff", b"\xff\x00") + b"\xff\xd9"
 
 
 # ---------------------------------------------------------------------------
@@ -232,3 +423,68 @@ def jpeg_roundtrip(x, quality, out=None):
             p.out = torch.empty_like(x)
         out = p.out
     return ops.jpeg_roundtrip(x, out, tables, p.ws)
+
+
+class _EncodePlan:
+    """The buffers of jpeg_encode at one (n, h, w, device): the workspace of the first half, and
+    the streams and files of the second, which grow to the longest scan seen."""
+
+    def __init__(self, n, h, w, device):
+        import torch
+        from . import ops
+        self.ws = torch.empty(ops.jpeg_encode_workspace_bytes(n, h, w), dtype=torch.uint8, device=device)
+        self.bits = torch.empty(n, dtype=torch.int64, device=device)
+        self.sizes = torch.empty(n, dtype=torch.int32, device=device)
+        self.stream_ws = self.out = None
+
+    def room(self, n, max_bits, header_bytes):
+        import torch
+        from . import ops
+        need, stride = ops.jpeg_encode_out_bytes(n, max_bits, header_bytes)
+        if self.out is None or self.stream_ws.numel() < need or self.out.shape[1] < stride:
+            self.stream_ws = torch.empty(need, dtype=torch.uint8, device=self.ws.device)
+            self.out = torch.empty((n, stride), dtype=torch.uint8, device=self.ws.device)
+        return self.stream_ws, self.out
+
+
+def jpeg_encode(x, quality):
+    """A dense uint8 NHWC device tensor [n,h,w,3] -> a list of n `bytes`, every image's baseline JPEG
+    file at `quality` and 4:2:0, equal to `jpeg_encode_ref` (and to the file Pillow writes) byte for
+    byte; [] for n = 0.  Colour, DCT, quantisation, Huffman coding and byte stuffing run on the
+    device (csrc/jpeg_enc.hip); what crosses to the host is n scan lengths, which size the streams,
+    n file lengths and the files themselves.  The call waits for those, so it cannot be captured
+    in a graph; its buffers are kept per shape in the round trip's plan cache."""
+    import torch
+    from . import ops
+    from .metrics import _lru
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise ValueError(f"jpeg_encode: expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 4 or x.shape[3] != 3 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"jpeg_encode: expected a dense [n,h,w,3] device tensor, got shape {tuple(x.shape)} on "
+                         f"{x.device}")
+    quality = _check_quality(quality, "jpeg_encode")
+    n, h, w, _ = x.shape
+    if min(h, w) < 1:
+        raise ValueError(f"jpeg_encode: empty image: {tuple(x.shape)}")
+    header = jpeg_header(h, w, quality)
+    if n == 0:
+        return []
+    p = _lru(_plans, ("encode", n, h, w, x.device), lambda: _EncodePlan(n, h, w, x.device), MAX_PLANS)
+    ops.jpeg_encode_scan(x, quant_tables(quality), p.ws, p.bits)
+    max_bits = int(p.bits.max().item())
+    stream_ws, out = p.room(n, max_bits, len(header))
+    ops.jpeg_encode_emit(x.shape, p.ws, p.bits, max_bits, header, stream_ws, out, p.sizes)
+    sizes = p.sizes.cpu().tolist()
+    if min(sizes) < len(header) + 2:
+        raise RuntimeError(f"jpeg_encode: the device reports file lengths {sizes}")
+    host = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+    at = 0
+    for i, size in enumerate(sizes):
+        host[at:at + size].copy_(out[i, :size], non_blocking=True)
+        at += size
+    torch.cuda.current_stream().synchronize()
+    data, files, at = host.numpy().tobytes(), [], 0
+    for size in sizes:
+        files.append(data[at:at + size])
+        at += size
+    return files

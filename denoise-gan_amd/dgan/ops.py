@@ -1263,6 +1263,73 @@ def jpeg_roundtrip(x, out, qtab, ws):
     return out
 
 
+# ---- JPEG encoder (include/dgan.h "Baseline JPEG encoder") ----------------------------------------
+def jpeg_encode_workspace_bytes(n, h, w):
+    nb = ctypes.c_size_t()
+    call("dg_jpeg_encode_ws_bytes", int(n), int(h), int(w), ctypes.byref(nb))
+    return nb.value
+
+
+def jpeg_encode_out_bytes(n, max_bits, header_bytes):
+    """-> (bytes of the stream workspace, bytes between two files of `out`) of jpeg_encode_emit."""
+    sb, stride = ctypes.c_size_t(), ctypes.c_size_t()
+    call("dg_jpeg_encode_out_bytes", int(n), int(max_bits), int(header_bytes), ctypes.byref(sb), ctypes.byref(stride))
+    return sb.value, stride.value
+
+
+def _jpeg_buf(t, dtype, numel, like, what):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or t.device != like.device
+            or t.numel() < numel):
+        raise DGError(f"{what}: expected a dense {dtype} buffer of at least {numel} elements on {like.device}")
+
+
+def jpeg_encode_scan(x, qtab, ws, bits):
+    """The first half of the encoder (dg_jpeg_encode_scan) on the dense uint8 images x[n,h,w,3]:
+    coefficients, block lengths and their scan into ws (uint8, jpeg_encode_workspace_bytes), every
+    image's scan length into bits (int64 [n]).  qtab: dgan.jpeg.quant_tables."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise DGError(f"jpeg_encode: expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[3] != 3:
+        raise DGError(f"jpeg_encode: expected dense [n,h,w,3] tensors, got shape {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise DGError("jpeg_encode: expected device tensors (the HIP path has no CPU fallback)")
+    q = np.asarray(qtab)
+    if q.dtype != np.uint8 or q.shape != (2, 64) or int(q.min()) < 1:
+        raise DGError(f"jpeg_encode: qtab must be uint8 [2,64] with entries >= 1, got {q.dtype} {q.shape}")
+    n, h, w, _ = x.shape
+    need = jpeg_encode_workspace_bytes(n, h, w)
+    if n:
+        _jpeg_buf(ws, torch.uint8, need, x, "jpeg_encode ws")
+        _jpeg_buf(bits, torch.int64, n, x, "jpeg_encode bits")
+    tables = (ctypes.c_ubyte * 128).from_buffer_copy(np.ascontiguousarray(q).tobytes())
+    call("dg_jpeg_encode_scan", n, h, w, _p(x), tables, _p(ws) if n else None, ws.numel() if n else 0,
+         _p(bits) if n else None, _stream())
+    return bits
+
+
+def jpeg_encode_emit(shape, ws, bits, max_bits, header, stream_ws, out, sizes):
+    """The second half (dg_jpeg_encode_emit) for images of `shape` [n,h,w,3]: ws and bits as
+    jpeg_encode_scan left them, max_bits the maximum of bits, header the host bytes from SOI to SOS;
+    stream_ws (uint8) and out (uint8 [n,stride]) sized by jpeg_encode_out_bytes, sizes int32 [n]:
+    out[i, :sizes[i]] is image i's file."""
+    n, h, w, _ = shape
+    header = bytes(header)
+    need_stream, need_stride = jpeg_encode_out_bytes(n, max_bits, len(header))
+    if n:
+        _jpeg_buf(ws, torch.uint8, jpeg_encode_workspace_bytes(n, h, w), ws, "jpeg_encode ws")
+        _jpeg_buf(bits, torch.int64, n, ws, "jpeg_encode bits")
+        _jpeg_buf(stream_ws, torch.uint8, need_stream, ws, "jpeg_encode stream_ws")
+        _jpeg_buf(sizes, torch.int32, n, ws, "jpeg_encode sizes")
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or not out.is_contiguous()
+                or out.device != ws.device or out.shape[0] != n or out.shape[1] < need_stride):
+            raise DGError(f"jpeg_encode out: expected a dense uint8 [{n}, >= {need_stride}] buffer on {ws.device}")
+    hdr = (ctypes.c_ubyte * max(len(header), 1)).from_buffer_copy(header or b"\0")
+    call("dg_jpeg_encode_emit", n, h, w, _p(ws) if n else None, ws.numel() if n else 0, _p(bits) if n else None,
+         int(max_bits), hdr, len(header), _p(stream_ws) if n else None, stream_ws.numel() if n else 0,
+         _p(out) if n else None, out.shape[1] if n else 0, _p(sizes) if n else None, _stream())
+    return sizes
+
+
 # ---- classical filters (include/dgan.h "Classical filters") -------------------------------------
 def _filter_pair(x, out, what):
     for t in (x, out):

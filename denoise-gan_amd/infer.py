@@ -8,7 +8,9 @@ that names the width.  Images are read and written with Pillow, as RGB; each kee
 file name.  Whole images are padded to a multiple of 256 by default; --tile T (a multiple of 256)
 with --margin M runs T x T tiles with M pixels of context instead, --batch of them per forward.
 --post median3 puts the denoised frame through a 3x3 median on the device before it is read back
-(dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).
+(dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).  --format jpg writes
+<stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
+only the file's bytes are read back.
 
 Deviation from the reference: the generator is fed [-1, 1] (uint8 / 255 * 2 - 1, what it was
 trained on, dataloader.py:173-175); the reference's infer.py:55 feeds [0, 1].
@@ -29,6 +31,9 @@ parser.add_argument("--pad", default="black", choices=["black", "reflect"], help
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
 parser.add_argument("--post", default=None, choices=["median3"],
                     help="A classical filter applied to the denoised image on the device (default: none).")
+parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
+                    help="keep: Pillow writes every image under its own name; jpg: baseline JPEG files encoded on the device.")
+parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
 
 
 def load_generator(model_path):
@@ -47,6 +52,8 @@ def main(argv=None):
     from PIL import Image
     from dgan.infer import Denoiser
     args = parser.parse_args(argv)
+    if not 1 <= args.jpeg_quality <= 100:
+        parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
     image_dir = os.path.expanduser(os.path.expandvars(args.image_dir))
     output_dir = os.path.expanduser(os.path.expandvars(args.output_dir))
     model_path = os.path.expanduser(os.path.expandvars(args.model))
@@ -57,6 +64,17 @@ def main(argv=None):
     for image_path in image_paths:
         with Image.open(image_path) as im:
             noisy = np.asarray(im.convert("RGB"), np.uint8)
+        if args.format == "jpg":
+            from dgan.jpeg import jpeg_encode
+            frame = denoiser.run(noisy[None]).u8_out
+            if args.post == "median3":
+                from dgan.filters import median3
+                frame = median3(frame)
+            out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
+            with open(out_path, "wb") as f:
+                f.write(jpeg_encode(frame, args.jpeg_quality)[0])
+            print(f"{image_path} -> {out_path} {noisy.shape[1]}x{noisy.shape[0]}")
+            continue
         if args.post == "median3":
             from dgan.filters import median3
             clean = median3(denoiser.run(noisy[None]).u8_out).cpu().numpy()[0]

@@ -10,7 +10,9 @@ srgan (--scale 2 or 4) or autoencoder (x1, inputs padded to a multiple of 32).  
 and written with Pillow, as RGB, under their file names.  Whole images by default; --tile T with
 --margin M runs T x T tiles with M pixels of context (10 cover FastSRGAN's receptive field, 36
 SRGAN's), --batch of them per forward.  --fp16 1 runs the 3x3 convs on the mixed_float16 policy;
-the fused FastSRGAN blocks stay fp32 (dgan/sr_infer.py).
+the fused FastSRGAN blocks stay fp32 (dgan/sr_infer.py).  --format jpg writes <stem>.jpg at
+--jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and only the
+file's bytes are read back.
 """
 import os
 from argparse import ArgumentParser
@@ -28,6 +30,9 @@ parser.add_argument("--margin", default=0, type=int, help="Context pixels on eac
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
 parser.add_argument("--fp16", default=0, type=int, help="Run the conv GEMMs on the mixed_float16 policy.")
+parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
+                    help="keep: Pillow writes every image under its own name; jpg: baseline JPEG files encoded on the device.")
+parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
 
 
 def load_network(arch, model_path, scale=4, fp16=False):
@@ -54,6 +59,8 @@ def main(argv=None):
     from PIL import Image
     from dgan.sr_infer import Upscaler
     args = parser.parse_args(argv)
+    if not 1 <= args.jpeg_quality <= 100:
+        parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
     image_dir = os.path.expanduser(os.path.expandvars(args.image_dir))
     output_dir = os.path.expanduser(os.path.expandvars(args.output_dir))
     model_path = os.path.expanduser(os.path.expandvars(args.model))
@@ -65,6 +72,14 @@ def main(argv=None):
     for image_path in image_paths:
         with Image.open(image_path) as im:
             low = np.asarray(im.convert("RGB"), np.uint8)
+        if args.format == "jpg":
+            from dgan.jpeg import jpeg_encode
+            frame = upscaler.run(low[None]).u8_out
+            out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
+            with open(out_path, "wb") as f:
+                f.write(jpeg_encode(frame, args.jpeg_quality)[0])
+            print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
+            continue
         high = upscaler.upscale(low)
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(high, "RGB").save(out_path)

@@ -694,6 +694,33 @@ int dg_jpeg_roundtrip_u8(int n, int h, int w, const unsigned char *in, unsigned 
                          void *ws, size_t ws_bytes, dg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Baseline JPEG encoder (dgan/jpeg.py jpeg_encode_ref: the file libjpeg writes at 4:2:0 with the
+ * Annex K Huffman tables, no restart markers).  Dense RGB images [n][h][w][3], any byte alignment,
+ * h and w in 1..65535; integers only.  Two calls with one read-back of n integers between them:
+ * dg_jpeg_encode_scan    the round trip's front end (colour, downsample, DCT, quantise; qtab as
+ *     above) into int16 coefficients [n][mcu][6][64] in zigzag and scan order with libjpeg's dummy
+ *     luma blocks filled in, every block's code length, and their exclusive scan per image.
+ *     bits: n DEVICE int64, the length of every image's entropy-coded scan before padding and
+ *     stuffing.  ws: dg_jpeg_encode_ws_bytes, 16-byte aligned; the second call reads it.
+ * dg_jpeg_encode_emit    ws, bits: the first call's; max_bits: the caller's maximum of bits[].  The
+ *     Huffman codes go MSB first into one zeroed stream per image, padded with 1 bits to a byte;
+ *     then every image's file is put together at out + i * out_stride: the `header_bytes` HOST
+ *     bytes of `header` (at most 640: SOI to SOS), the stream with 0x00 after every 0xFF, EOI.
+ *     sizes: n DEVICE int32, the file lengths; -1 for an image whose bits[] exceeds max_bits
+ *     (nothing of it is written).
+ *     stream_ws (16-byte aligned) and out_stride (the room of one file, a multiple of 4) are sized
+ *     by dg_jpeg_encode_out_bytes for the same n, max_bits and header_bytes.
+ * Eight launches in all.  The caller sizes buffers from device results, so the pair cannot be
+ * captured in a graph. */
+int dg_jpeg_encode_ws_bytes(int n, int h, int w, size_t *bytes);
+int dg_jpeg_encode_scan(int n, int h, int w, const unsigned char *in, const unsigned char *qtab, void *ws,
+                        size_t ws_bytes, long long *bits, dg_stream_t stream);
+int dg_jpeg_encode_out_bytes(int n, long long max_bits, int header_bytes, size_t *stream_bytes, size_t *out_stride);
+int dg_jpeg_encode_emit(int n, int h, int w, const void *ws, size_t ws_bytes, const long long *bits,
+                        long long max_bits, const unsigned char *header, int header_bytes, void *stream_ws, size_t stream_bytes,
+                        unsigned char *out, size_t out_stride, int *sizes, dg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Classical filters (dgan/filters.py median3_ref / nlm_ref).  Dense RGB images [n][h][w][3] ->
  * the same shape, any byte alignment; integer arithmetic only, so the results equal the numpy
  * references bit for bit and two calls give the same bits.  One launch each, no workspace; `out`
