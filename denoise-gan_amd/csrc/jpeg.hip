@@ -9,40 +9,13 @@
 //                  the colour conversion back
 // int32 throughout, no floating point.  The first kernel has read all of `in` before the second
 // writes `out`, so the two may be one buffer.  The first kernel's front half, up to the quantised
-// levels, is jpeg_front.h's, which the encoder (jpeg_enc.hip) shares.
-#include "jpeg_front.h"
+// levels, is jpeg_front.h's, which the encoder (jpeg_enc.hip) shares; the inverse DCT, the range
+// limit and the second kernel's launch are jpeg_back.h's, which the decoder (jpeg_dec.hip) shares.
+#include "jpeg_back.h"
 
 namespace dg {
 
 constexpr int JBW = 64, JBH = 4;    // k_jpeg_pixels: a thread block covers 256 x 4 pixels
-
-__host__ __device__ __forceinline__ long jpeg_image_bytes(int Hp, int Wp) { return (long)Hp * Wp / 2 * 3; }
-
-// one jidctint pass in place: FIRST the column pass (descaled by 11), else the row pass (by 18)
-template <bool FIRST>
-__device__ __forceinline__ void jpeg_idct8(int c[8]) {
-    const int z1 = (c[2] + c[6]) * 4433;
-    const int t2 = z1 - c[6] * 15137, t3 = z1 + c[2] * 6270;
-    const int t0 = (c[0] + c[4]) * 8192, t1 = (c[0] - c[4]) * 8192;
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    int a0 = c[7], a1 = c[5], a2 = c[3], a3 = c[1];
-    jpeg_odd(a0, a1, a2, a3);
-    constexpr int n = FIRST ? 11 : 18;
-    c[0] = jpeg_descale(t10 + a3, n);
-    c[7] = jpeg_descale(t10 - a3, n);
-    c[1] = jpeg_descale(t11 + a2, n);
-    c[6] = jpeg_descale(t11 - a2, n);
-    c[2] = jpeg_descale(t12 + a1, n);
-    c[5] = jpeg_descale(t12 - a1, n);
-    c[3] = jpeg_descale(t13 + a0, n);
-    c[4] = jpeg_descale(t13 - a0, n);
-}
-
-// libjpeg's range-limit table read at x & 1023
-__device__ __forceinline__ unsigned jpeg_limit(int x) {
-    x &= 1023;
-    return x < 128 ? x + 128 : x < 512 ? 255 : x < 896 ? 0 : x - 896;
-}
 
 // grid (strips along w, strips along h, n)
 __global__ void __launch_bounds__(JT)
@@ -141,6 +114,14 @@ k_jpeg_pixels(JpegArgs A, const unsigned char *__restrict__ ws, unsigned char *_
     }
 }
 
+int jpeg_launch_pixels(const char *name, const JpegArgs &A, int n, const unsigned char *ws, unsigned char *out,
+                       hipStream_t stream) {
+    hipLaunchKernelGGL(k_jpeg_pixels, dim3(dg_cdiv(dg_cdiv(A.w, 4), JBW), dg_cdiv(A.h, JBH), n), dim3(JBW, JBH), 0,
+                       stream, A, ws, out);
+    DG_LAUNCHED(name);
+    return DG_OK;
+}
+
 }  // namespace dg
 
 int dg_jpeg_ws_bytes(int n, int h, int w, size_t *bytes) {
@@ -170,8 +151,5 @@ int dg_jpeg_roundtrip_u8(int n, int h, int w, const unsigned char *in, unsigned 
     hipLaunchKernelGGL(k_jpeg_blocks, dim3(A.Wp / JSW, A.Hp / JSH, n), dim3(JT), 0, (hipStream_t)stream, A, Q, in,
                        (unsigned char *)ws);
     DG_LAUNCHED("jpeg_roundtrip_u8 (blocks)");
-    hipLaunchKernelGGL(k_jpeg_pixels, dim3(dg_cdiv(dg_cdiv(w, 4), JBW), dg_cdiv(h, JBH), n), dim3(JBW, JBH), 0,
-                       (hipStream_t)stream, A, (const unsigned char *)ws, out);
-    DG_LAUNCHED("jpeg_roundtrip_u8 (pixels)");
-    return DG_OK;
+    return jpeg_launch_pixels("jpeg_roundtrip_u8 (pixels)", A, n, (const unsigned char *)ws, out, (hipStream_t)stream);
 }

@@ -166,6 +166,11 @@ _SIGS = {
     "dg_jpeg_encode_out_bytes": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
     "dg_jpeg_encode_emit": (c_int, [c_int] * 3 + [_P, c_size_t, _P, c_int64, c_void_p, c_int, _P, c_size_t, _P, c_size_t,
                                     _P, _P]),
+    "dg_jpeg_decode_geometry": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "dg_jpeg_decode_ws_bytes": (c_int, [c_int] * 3 + [c_int64, ctypes.POINTER(c_size_t)]),
+    "dg_jpeg_decode_scan": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, _P]),
+    "dg_jpeg_decode_sync": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, c_int, _P]),
+    "dg_jpeg_decode_pixels": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, _P, _P]),
     "dg_median3_u8": (c_int, [c_int] * 3 + [_P, _P, _P]),
     "dg_nlm_u8": (c_int, [c_int] * 5 + [_P, c_int, _P, _P, _P]),
 }

@@ -390,12 +390,13 @@ class Denoiser:
         return f
 
     def run(self, images):
-        """Upload uint8 numpy images [n,h,w,3] (n >= 1) and denoise them on the current stream
+        """Upload uint8 numpy images [n,h,w,3] (n >= 1), or take a dense uint8 device tensor of that
+        shape (dgan.jpeg.jpeg_decode's: a device copy, no upload), and denoise them on the current stream
         without reading anything back: the frame whose device buffers `u8_in` / `u8_out` hold the
         input and the result until the next call on the same shape (dgan/metrics.py Evaluator)."""
         import torch
         f = self._frame(*images.shape[:3])
-        f.u8_in.copy_(torch.from_numpy(np.ascontiguousarray(images)))
+        f.u8_in.copy_(images if isinstance(images, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(images)))
         if f.graph is not None:
             f.graph.replay()
         else:

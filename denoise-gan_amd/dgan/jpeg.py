@@ -35,7 +35,13 @@ The encoder finishes the codec: `jpeg_encode_ref` Huffman-codes the same quantis
 baseline file Pillow writes (header, scan order, dummy blocks and coding rules: DESIGN.md section JPEG
 encoder), and `jpeg_encode` is the device op (csrc/jpeg_enc.hip), equal to it byte for byte.
 
-`quant_tables`, `jpeg_ref` and `jpeg_encode_ref` are pure numpy and import neither torch nor the library.
+The decoder reads such files back: `jpeg_parse` reads a header, `jpeg_decode_ref` is the definition
+(a sequential Huffman decode, then the round trip's back half; equal to Pillow's decoder), and
+`jpeg_decode` is the device op (csrc/jpeg_dec.hip), equal to it bit for bit (DESIGN.md section JPEG
+decoder).
+
+`quant_tables`, `jpeg_ref`, `jpeg_encode_ref`, `jpeg_parse` and `jpeg_decode_ref` are pure numpy and
+import neither torch nor the library.
 """
 import numpy as np
 
@@ -123,13 +129,18 @@ def _quantise(plane, table):
     return np.sign(c) * ((np.abs(c) + 4 * t) // (8 * t))
 
 
-def _codec(plane, table):
-    """A plane [n,H,W] (H, W multiples of 8) through the block pipeline with the table [64]."""
-    n, H, W = plane.shape
-    c = _quantise(plane, table) * table.astype(plane.dtype).reshape(8, 8)
+def _inverse(c):
+    """Dequantised coefficients [n,by,bx,row,col] -> the decoded samples [n,8 by,8 bx]: jidctint and
+    the range limit."""
+    n, by, bx = c.shape[:3]
     x = _along(_idct_1d, _along(_idct_1d, c, 3, True), 4, False) & 1023
     x = np.where(x < 128, x + 128, np.where(x < 512, 255, np.where(x < 896, 0, x - 896)))
-    return x.transpose(0, 1, 3, 2, 4).reshape(n, H, W)
+    return x.transpose(0, 1, 3, 2, 4).reshape(n, by * 8, bx * 8)
+
+
+def _codec(plane, table):
+    """A plane [n,H,W] (H, W multiples of 8) through the block pipeline with the table [64]."""
+    return _inverse(_quantise(plane, table) * table.astype(plane.dtype).reshape(8, 8))
 
 
 def _edge(p, H, W):
@@ -188,19 +199,20 @@ def jpeg_ref(img_u8, quality, dtype=np.int64):
     if single:
         a = a[None]
     n, h, w = a.shape[:3]
-    ch, cw = -(-h // 2), -(-w // 2)
     Y, Cb, Cr = _planes(a, dtype)
-    Y = _codec(Y, tables[0])[:, :h, :w]
-    chroma = []
-    for C in (Cb, Cr):
-        C = _codec(C, tables[1])[:, :ch, :cw]
-        chroma.append(_upsample(C, cw > 2)[:, :h, :w] - 128)
-    Cb, Cr = chroma
+    out = _pixels(_codec(Y, tables[0]), _codec(Cb, tables[1]), _codec(Cr, tables[1]), h, w)
+    return out[0] if single else out
+
+
+def _pixels(Y, Cb, Cr, h, w):
+    """The decoded planes [n,H,W] and [n,Hc,Wc] -> uint8 [n,h,w,3] (module docstring: decode)."""
+    ch, cw = -(-h // 2), -(-w // 2)
+    Y = Y[:, :h, :w]
+    Cb, Cr = (_upsample(C[:, :ch, :cw], cw > 2)[:, :h, :w] - 128 for C in (Cb, Cr))
     out = np.stack([Y + ((_fix(1.402) * Cr + 32768) >> 16),
                     Y + ((-_fix(.34414) * Cb + 32768 - _fix(.71414) * Cr) >> 16),
                     Y + ((_fix(1.772) * Cb + 32768) >> 16)], axis=-1)
-    out = np.clip(out, 0, 255).astype(np.uint8)
-    return out[0] if single else out
+    return np.clip(out, 0, 255).astype(np.uint8)
 
 
 # ---------------------------------------------------------------------------
@@ -373,6 +385,263 @@ def jpeg_encode_ref(img_u8, quality):
 
 
 # ---------------------------------------------------------------------------
+# the baseline decoder: header parser, the definition, the device tables (csrc/jpeg_dec.hip)
+# ---------------------------------------------------------------------------
+class JpegUnsupported(ValueError):
+    """A file outside what the decoder reads: baseline, 8 bits, 4:2:0 in one interleaved scan."""
+
+
+class JpegInfo:
+    """What `jpeg_parse` reads from a header.  h, w; quant {id: uint8 [64], natural order};
+    components ((quant, dc, ac) table ids of Y, Cb, Cr); huffman {(class, id): (bits[16], values)},
+    class 0 DC and 1 AC; scan (first, end) the byte range of the entropy-coded data."""
+    __slots__ = ("h", "w", "quant", "components", "huffman", "scan")
+
+    def __init__(self, h, w, quant, components, huffman, scan):
+        self.h, self.w, self.quant, self.components, self.huffman, self.scan = h, w, quant, components, huffman, scan
+
+
+def _huffman_codes_ok(bits):
+    code = 0
+    for length in range(1, 17):
+        code = (code + bits[length - 1]) << 1
+        if code > (2 << length):
+            return False
+    return True
+
+
+def jpeg_parse(data):
+    """The header of a JPEG file (`bytes`) -> JpegInfo.  Reads the marker segments up to SOS and
+    finds the scan's end with `bytes.rfind`; APPn and COM segments are skipped.  JpegUnsupported,
+    with the reason, for a file that is not SOF0 at 8 bits with three components sampled 2x2, 1x1,
+    1x1 in one interleaved scan, Huffman table ids 0 / 1, no restart interval, no Adobe segment and
+    component ids other than R, G, B."""
+    if not isinstance(data, bytes):
+        raise TypeError(f"jpeg_parse: expected bytes, got {type(data).__name__}")
+    if data[:2] != b"\xff\xd8":
+        raise JpegUnsupported("not a JPEG file (no SOI marker)")
+    quant, huffman, frame, at = {}, {}, None, 2
+    while True:
+        if at + 4 > len(data) or data[at] != 0xFF:
+            raise JpegUnsupported(f"no marker at byte {at}")
+        marker = data[at + 1]
+        if marker == 0xFF:   # a fill byte
+            at += 1
+            continue
+        size = int.from_bytes(data[at + 2:at + 4], "big")
+        seg = data[at + 4:at + 2 + size]
+        if size < 2 or len(seg) != size - 2:
+            raise JpegUnsupported(f"segment {marker:#x} at byte {at} is cut off")
+        at += 2 + size
+        if marker == 0xDB:
+            while seg:
+                if seg[0] >> 4 or len(seg) < 65:
+                    raise JpegUnsupported("a quantisation table of 16 bits")
+                natural = np.zeros(64, np.uint8)
+                natural[list(ZIGZAG)] = np.frombuffer(seg[1:65], np.uint8)
+                quant[seg[0] & 15] = natural
+                seg = seg[65:]
+        elif marker == 0xC4:
+            while seg:
+                cls, ident, bits = seg[0] >> 4, seg[0] & 15, tuple(seg[1:17])
+                count = sum(bits)
+                if cls > 1 or ident > 1 or len(seg) < 17 + count or count > 256 or not _huffman_codes_ok(bits):
+                    raise JpegUnsupported(f"Huffman table class {cls} id {ident}: ids 0 and 1 of well-formed tables only")
+                huffman[(cls, ident)] = (bits, tuple(seg[17:17 + count]))
+                seg = seg[17 + count:]
+        elif marker == 0xC0:
+            if len(seg) < 6 or seg[0] != 8:
+                raise JpegUnsupported(f"sample precision {seg[0] if seg else None}, not 8 bits")
+            h, w, nf = int.from_bytes(seg[1:3], "big"), int.from_bytes(seg[3:5], "big"), seg[5]
+            comps = [tuple(seg[6 + 3 * k:9 + 3 * k]) for k in range(nf)]
+            if nf != 3 or len(seg) < 15:
+                raise JpegUnsupported(f"{nf} components, not 3")
+            if [c[1] for c in comps] != [0x22, 0x11, 0x11]:
+                raise JpegUnsupported("sampling factors " + " ".join(f"{c[1] >> 4}x{c[1] & 15}" for c in comps) +
+                                      ", not 2x2 1x1 1x1 (4:2:0)")
+            if bytes(c[0] for c in comps) == b"RGB":
+                raise JpegUnsupported("component ids R, G, B: an RGB file, not YCbCr")
+            if h < 1 or w < 1:
+                raise JpegUnsupported(f"image size {h}x{w}")
+            frame = (h, w, comps)
+        elif 0xC1 <= marker <= 0xCF and marker != 0xC8:
+            raise JpegUnsupported(f"frame type SOF{marker - 0xC0}" + (" (progressive)" if marker == 0xC2 else "") +
+                                  ", not baseline SOF0")
+        elif marker == 0xDD:
+            if int.from_bytes(seg[:2], "big"):
+                raise JpegUnsupported("restart intervals (DRI)")
+        elif marker == 0xEE and seg[:5] == b"Adobe":
+            raise JpegUnsupported("an Adobe APP14 segment")
+        elif marker == 0xDA:
+            break
+    if frame is None:
+        raise JpegUnsupported("SOS before SOF0")
+    h, w, comps = frame
+    if len(seg) != 10 or seg[0] != 3 or [seg[1 + 2 * k] for k in range(3)] != [c[0] for c in comps]:
+        raise JpegUnsupported("the scan does not interleave the three components")
+    if tuple(seg[7:10]) != (0, 63, 0):
+        raise JpegUnsupported(f"scan parameters Ss {seg[7]} Se {seg[8]} Ah/Al {seg[9]:#x}, not 0 63 0")
+    components = tuple((comps[k][2], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(3))
+    for q, dc, ac in components:
+        if q not in quant or (0, dc) not in huffman or (1, ac) not in huffman:
+            raise JpegUnsupported(f"a component names a table the file does not define: quant {q}, DC {dc}, AC {ac}")
+    end = data.rfind(b"\xff\xd9")
+    if end < at:
+        raise JpegUnsupported("no EOI marker after the scan")
+    return JpegInfo(h, w, quant, components, huffman, (at, end))
+
+
+def _huffman_lookup(bits, values):
+    """A table as (bits[16], values) -> int64 [65536]: (length << 8) | symbol of the code a 16-bit
+    window starts with, 0 where it starts with none."""
+    lut, code, i = np.zeros(65536, np.int64), 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            lut[code << (16 - length):(code + 1) << (16 - length)] = (length << 8) | values[i]
+            code, i = code + 1, i + 1
+        code <<= 1
+    return lut
+
+
+def scan_levels(info, data):
+    """The entropy-coded scan of `data` (info = jpeg_parse(data)) -> int64 [mcu,6,64]: the
+    quantised levels in zigzag order, DC differences summed per component, by a plain sequential
+    Huffman decode.  0x00 after 0xFF is stuffing; bits after the last block are ignored.
+    ValueError when the bits run out first or start no code."""
+    scan = data[info.scan[0]:info.scan[1]].replace(b"\xff\x00", b"\xff")
+    total = 8 * len(scan)
+    scan += bytes(8)
+    luts = {k: _huffman_lookup(*t).tolist() for k, t in info.huffman.items()}
+    mcus = -(-info.h // 16) * -(-info.w // 16)
+    out = np.zeros((mcus, 6, 64), np.int64)
+    p, pred = 0, [0, 0, 0]
+    for m in range(mcus):
+        for b in range(6):
+            comp = max(b - 3, 0)
+            dc, ac = luts[(0, info.components[comp][1])], luts[(1, info.components[comp][2])]
+            k = 0
+            while k < 64:
+                window = (int.from_bytes(scan[p >> 3:(p >> 3) + 5], "big") >> (8 - (p & 7))) & 0xFFFFFFFF
+                e = (ac if k else dc)[window >> 16]
+                length, run, size = e >> 8, (e >> 4) & 15, e & 15
+                if not e:
+                    raise ValueError(f"jpeg_decode_ref: no Huffman code at bit {p} of the scan (block {6 * m + b})")
+                if p + length + size > total:
+                    raise ValueError(f"jpeg_decode_ref: the scan ends in block {6 * m + b} of {6 * mcus}")
+                v = (window >> (32 - length - size)) & ((1 << size) - 1) if size else 0
+                if size and v < (1 << (size - 1)):
+                    v -= (1 << size) - 1
+                p += length + size
+                if k == 0:
+                    pred[comp] += v
+                    out[m, b, 0] = pred[comp]
+                    k = 1
+                elif size == 0:
+                    k = k + 16 if run == 15 else 64
+                else:
+                    k += run
+                    if k < 64:
+                        out[m, b, k] = v
+                    k += 1
+    return out
+
+
+def jpeg_decode_ref(data):
+    """The decoder's definition on the host: the bytes of a baseline 4:2:0 JPEG file (what
+    `jpeg_parse` accepts) -> uint8 [h,w,3], what Pillow's `Image.open().convert("RGB")` returns: the
+    sequential Huffman decode of `scan_levels`, then the back half of `jpeg_ref` with every
+    component's own quantisation table."""
+    info = jpeg_parse(data)
+    h, w = info.h, info.w
+    my, mx = -(-h // 16), -(-w // 16)
+    lv = scan_levels(info, data)
+    c = np.zeros_like(lv)
+    c[..., list(ZIGZAG)] = lv
+    c = c.reshape(my, mx, 6, 8, 8)
+    q = [info.quant[info.components[k][0]].astype(np.int64).reshape(8, 8) for k in range(3)]
+    luma = c[:, :, :4].reshape(my, mx, 2, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(1, 2 * my, 2 * mx, 8, 8)
+    planes = [_inverse(luma * q[0])] + [_inverse(c[None, :, :, 3 + k] * q[k]) for k in (1, 2)]
+    return _pixels(planes[0], planes[1], planes[2], h, w)[0]
+
+
+# the decoder's device tables (csrc/jpeg_dec.hip): sizes in bytes and 32-bit words
+DECODE_SUBSEQUENCE = 128   # bytes of the unstuffed scan a lane decodes
+DECODE_LANES = 256         # lanes (subsequences) of a workgroup
+_LUT_BITS = 9
+_TABLE_WORDS = 256 + 18 + 18 + 64
+_DESC_WORDS = 4 + 48
+_table_cache = {}
+
+
+def _device_table(table):
+    """(bits[16], values) or None -> uint32 [_TABLE_WORDS]: a first-level table of 2^9 uint16
+    entries (length << 8) | symbol (0: a longer code), then libjpeg's slow path: maxcode[18] (-1: no
+    code of that length), valptr - mincode [18], the 256 symbols."""
+    out = np.zeros(_TABLE_WORDS, np.uint32)
+    lut, maxcode, valoff, vals = np.zeros(512, np.uint16), np.full(18, -1, np.int32), np.zeros(18, np.int32), \
+        np.zeros(256, np.uint8)
+    if table is not None:
+        bits, values = table
+        vals[:len(values)] = values
+        code, i = 0, 0
+        for length in range(1, 17):
+            valoff[length] = i - code
+            for _ in range(bits[length - 1]):
+                if length <= _LUT_BITS:
+                    lut[code << (_LUT_BITS - length):(code + 1) << (_LUT_BITS - length)] = (length << 8) | values[i]
+                code, i = code + 1, i + 1
+            if bits[length - 1]:
+                maxcode[length] = code - 1
+            code <<= 1
+    out[:256], out[256:274], out[274:292], out[292:] = lut.view(np.uint32), maxcode.view(np.uint32), \
+        valoff.view(np.uint32), vals.view(np.uint32)
+    return out
+
+
+def _device_tables(info):
+    """-> (key, the four tables DC0, DC1, AC0, AC1 of a file as one uint32 array), cached on their
+    contents, the key (nearly every file carries Annex K).  The cache may drop any entry at a later
+    call: a caller keeps the array it got."""
+    key = tuple(info.huffman.get(k) for k in ((0, 0), (0, 1), (1, 0), (1, 1)))
+    if key not in _table_cache:
+        if len(_table_cache) >= 64:
+            _table_cache.clear()
+        _table_cache[key] = np.concatenate([_device_table(t) for t in key])
+    return key, _table_cache[key]
+
+
+def _decode_blob(infos, files):
+    """What one upload carries (csrc/jpeg_dec.hip "the blob"): per image a descriptor of
+    _DESC_WORDS words (scan offset, scan bytes, offset of its tables, the components' table
+    selectors, the three quantisation tables), the distinct table sets, the scans, each at a
+    multiple of 16 bytes and followed by at least 16 zero bytes.  -> (uint8 array, longest scan)."""
+    n = len(files)
+    sets, order, which = {}, [], []   # distinct table sets by content, their arrays, every file's set
+    for info in infos:
+        key, t = _device_tables(info)
+        if key not in sets:
+            sets[key] = len(order)
+            order.append(t)
+        which.append(sets[key])
+    at = n * _DESC_WORDS * 4 + len(order) * 4 * _TABLE_WORDS * 4
+    starts = []
+    for info in infos:
+        starts.append(at)
+        at += -(-(info.scan[1] - info.scan[0]) // 16) * 16 + 16
+    blob = np.zeros(at, np.uint8)
+    words = blob[:n * _DESC_WORDS * 4].view(np.uint32).reshape(n, _DESC_WORDS)
+    for i, (info, data) in enumerate(zip(infos, files)):
+        first, end = info.scan
+        sel = sum(((dc & 1) | ((ac & 1) << 1)) << (2 * k) for k, (_, dc, ac) in enumerate(info.components))
+        words[i, :4] = starts[i], end - first, (n * _DESC_WORDS + which[i] * 4 * _TABLE_WORDS) * 4, sel
+        words[i, 4:] = np.concatenate([info.quant[c[0]] for c in info.components]).view(np.uint32)
+        blob[starts[i]:starts[i] + end - first] = np.frombuffer(data, np.uint8, end - first, first)
+    tabs = blob[n * _DESC_WORDS * 4:n * _DESC_WORDS * 4 + len(order) * 4 * _TABLE_WORDS * 4].view(np.uint32)
+    tabs[:] = np.concatenate(order)
+    return blob, max(info.scan[1] - info.scan[0] for info in infos)
+
+
+# ---------------------------------------------------------------------------
 # device code below: torch and the library are imported on use
 # ---------------------------------------------------------------------------
 class _Plan:
@@ -488,3 +757,107 @@ def jpeg_encode(x, quality):
         files.append(data[at:at + size])
         at += size
     return files
+
+
+class _DecodePlan:
+    """The buffers of jpeg_decode at one (n, h, w, device): the pinned blob and its device copy
+    and the workspace, which grow to the largest blob and the longest scan seen, and the output of
+    the calls without `out`."""
+
+    def __init__(self):
+        self.host = self.blob = self.ws = self.out = None
+        self.max_scan = -1
+
+    def room(self, n, h, w, device, blob_bytes, max_scan):
+        import torch
+        from . import ops
+        if self.host is None or self.host.numel() < blob_bytes:
+            self.host = torch.empty(blob_bytes + blob_bytes // 4, dtype=torch.uint8, pin_memory=True)
+            self.blob = torch.empty(self.host.numel(), dtype=torch.uint8, device=device)
+        if max_scan > self.max_scan:
+            self.max_scan = max_scan + max_scan // 4
+            self.ws = torch.empty(ops.jpeg_decode_workspace_bytes(n, h, w, self.max_scan), dtype=torch.uint8, device=device)
+
+
+def jpeg_decode(files, out=None, device=None):
+    """A list of n `bytes`, baseline 4:2:0 JPEG files of one size h x w (what `jpeg_parse` accepts;
+    their tables may differ) -> a dense uint8 [n,h,w,3] device tensor equal to
+    `np.stack([jpeg_decode_ref(f) for f in files])` bit for bit: `out`, or the plan's own buffer,
+    which the next call on the same shape overwrites.  [] gives an empty [0,0,0,3] tensor.  The
+    host parses the headers, looks up the Huffman tables' device form and uploads one pinned blob;
+    it never walks a scan.  Entropy decoding, DC prediction, IDCT, upsampling and colour run on
+    the device (csrc/jpeg_dec.hip).  The call reads one word per synchronisation round and the
+    status words at the end, so it cannot be captured in a graph.  ValueError, naming the file,
+    for a scan that ends early; files of different sizes; anything `jpeg_parse` refuses.  Only a
+    short scan is detected: damaged bits that still fill every block decode to unspecified pixels,
+    where `jpeg_decode_ref` raises for a window that starts no code."""
+    return _decode(files, out, device)[0]
+
+
+_STATUS = ((1, "the scan ends before the image's last block"), (2, "a symbol reaches past the scan's end"),
+           (4, "its descriptor points outside the uploaded blob"))
+
+
+def _decode(files, out, device):
+    """jpeg_decode -> (the tensor, the synchronisation rounds across workgroups the call ran)."""
+    import torch
+    from . import ops
+    from .metrics import _lru
+    files = list(files)
+    for i, f in enumerate(files):
+        if not isinstance(f, bytes):
+            raise TypeError(f"jpeg_decode: file {i} is {type(f).__name__}, not bytes")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"jpeg_decode: expected a GPU device (the HIP path has no CPU fallback), got {device}")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    n = len(files)
+    if n == 0:
+        if out is None:
+            return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=device), 0
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] != 0
+                or out.shape[3] != 3 or out.device != device):
+            raise ValueError(f"jpeg_decode: out must be a uint8 [0,h,w,3] tensor on {device}, got "
+                             f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        return out, 0
+    infos = [jpeg_parse(f) for f in files]
+    h, w = infos[0].h, infos[0].w
+    for i, info in enumerate(infos):
+        if (info.h, info.w) != (h, w):
+            raise ValueError(f"jpeg_decode: file {i} is {info.h}x{info.w}, file 0 is {h}x{w}: one call decodes one size")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (n, h, w, 3)
+                            or not out.is_contiguous() or out.device != device):
+        raise ValueError(f"jpeg_decode: out must be a dense uint8 {(n, h, w, 3)} tensor on {device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+    if (DECODE_SUBSEQUENCE, DECODE_LANES) != ops.jpeg_decode_geometry():
+        raise RuntimeError(f"jpeg_decode: the library decodes {ops.jpeg_decode_geometry()}, not "
+                           f"{(DECODE_SUBSEQUENCE, DECODE_LANES)} bytes x lanes")
+    blob, max_scan = _decode_blob(infos, files)
+    p = _lru(_plans, ("decode", n, h, w, device), _DecodePlan, MAX_PLANS)
+    with torch.cuda.device(device):
+        p.room(n, h, w, device, blob.size, max_scan)
+        p.host[:blob.size].numpy()[:] = blob
+        p.blob[:blob.size].copy_(p.host[:blob.size], non_blocking=True)
+        if out is None:
+            if p.out is None:
+                p.out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
+            out = p.out
+        call = ops.JpegDecodeCall(n, h, w, p.blob, blob.size, max_scan, p.ws)
+        call.scan()
+        groups = -(-max(-(-max_scan // DECODE_SUBSEQUENCE), 1) // DECODE_LANES)
+        seen = done = 0
+        for r in range(1, groups):   # after round r the workgroups 0..r of every image are final
+            call.sync(r)
+            done = r
+            moved = call.rounds_changed()
+            if moved == seen:
+                break
+            seen = moved
+        call.pixels(out)
+        status = call.status()
+    bad = [i for i, s in enumerate(status) if s]
+    if bad:
+        why = "; ".join(text for bit, text in _STATUS if status[bad[0]] & bit)
+        raise ValueError(f"jpeg_decode: file {bad[0]}: {why} (status {status[bad[0]]}; {len(bad)} of {n} files)")
+    return out, done

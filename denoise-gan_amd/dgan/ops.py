@@ -1330,6 +1330,57 @@ def jpeg_encode_emit(shape, ws, bits, max_bits, header, stream_ws, out, sizes):
     return sizes
 
 
+# ---- JPEG decoder (include/dgan.h "Baseline JPEG decoder") ----------------------------------------
+def jpeg_decode_geometry():
+    """-> (bytes of a subsequence, subsequences of a workgroup) of the entropy decoder."""
+    sub, lanes = ctypes.c_int(), ctypes.c_int()
+    call("dg_jpeg_decode_geometry", ctypes.byref(sub), ctypes.byref(lanes))
+    return sub.value, lanes.value
+
+
+def jpeg_decode_workspace_bytes(n, h, w, max_scan):
+    nb = ctypes.c_size_t()
+    call("dg_jpeg_decode_ws_bytes", int(n), int(h), int(w), int(max_scan), ctypes.byref(nb))
+    return nb.value
+
+
+class JpegDecodeCall:
+    """One decode of n files of h x w: `blob` the uploaded uint8 device buffer of dgan.jpeg's
+    _decode_blob (its first blob_bytes bytes), max_scan the longest scan, ws a uint8 device
+    workspace of jpeg_decode_workspace_bytes.  scan(), then sync(r) for r = 1, 2, ... while
+    `rounds_changed()` moves, then pixels(out); `status()` after that."""
+
+    def __init__(self, n, h, w, blob, blob_bytes, max_scan, ws):
+        self.n, self.h, self.w, self.max_scan, self.blob_bytes = int(n), int(h), int(w), int(max_scan), int(blob_bytes)
+        need = jpeg_decode_workspace_bytes(n, h, w, max_scan)
+        _jpeg_buf(ws, torch.uint8, need, ws, "jpeg_decode ws")
+        _jpeg_buf(blob, torch.uint8, self.blob_bytes, ws, "jpeg_decode blob")
+        if not ws.is_cuda:
+            raise DGError("jpeg_decode: expected device tensors (the HIP path has no CPU fallback)")
+        self.blob, self.ws = blob, ws
+        self.args = (self.n, self.h, self.w, _p(blob), self.blob_bytes, self.max_scan, _p(ws), ws.numel())
+
+    def scan(self):
+        call("dg_jpeg_decode_scan", *self.args, _stream())
+
+    def sync(self, r):
+        call("dg_jpeg_decode_sync", *self.args, int(r), _stream())
+
+    def rounds_changed(self):
+        return int(self.ws[:4].view(torch.int32).item())
+
+    def pixels(self, out):
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (self.n, self.h, self.w, 3)
+                or not out.is_contiguous() or out.device != self.ws.device):
+            raise DGError(f"jpeg_decode out: expected a dense uint8 {(self.n, self.h, self.w, 3)} tensor on "
+                          f"{self.ws.device}")
+        call("dg_jpeg_decode_pixels", *self.args, _p(out), _stream())
+        return out
+
+    def status(self):
+        return self.ws[16:16 + 4 * self.n].view(torch.int32).cpu().tolist()
+
+
 # ---- classical filters (include/dgan.h "Classical filters") -------------------------------------
 def _filter_pair(x, out, what):
     for t in (x, out):

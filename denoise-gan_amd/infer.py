@@ -10,7 +10,9 @@ with --margin M runs T x T tiles with M pixels of context instead, --batch of th
 --post median3 puts the denoised frame through a 3x3 median on the device before it is read back
 (dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).  --format jpg writes
 <stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
-only the file's bytes are read back.
+only the file's bytes are read back.  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
+and decodes them on the device (dgan.jpeg.jpeg_decode); every other file goes through Pillow, with
+a line that says why.
 
 Deviation from the reference: the generator is fed [-1, 1] (uint8 / 255 * 2 - 1, what it was
 trained on, dataloader.py:173-175); the reference's infer.py:55 feeds [0, 1].
@@ -34,6 +36,8 @@ parser.add_argument("--post", default=None, choices=["median3"],
 parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
                     help="keep: Pillow writes every image under its own name; jpg: baseline JPEG files encoded on the device.")
 parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
+parser.add_argument("--decode", default="pillow", choices=["pillow", "device"],
+                    help="device: baseline 4:2:0 .jpg / .jpeg files are decoded on the device; every other file through Pillow.")
 
 
 def load_generator(model_path):
@@ -46,6 +50,26 @@ def load_generator(model_path):
     g = Generator(width=int(meta["width"]))
     g.load_weights(base + ".npz")
     return g
+
+
+def read_image(image_path, decode):
+    """-> uint8 [1,h,w,3]: a device tensor from dgan.jpeg.jpeg_decode for --decode device and a file
+    it reads, else the numpy array Pillow decodes."""
+    from PIL import Image
+    if decode == "device":
+        from dgan.jpeg import JpegUnsupported, jpeg_decode, jpeg_parse
+        why = "not a .jpg / .jpeg file"
+        if image_path.lower().endswith((".jpg", ".jpeg")):
+            with open(image_path, "rb") as f:
+                data = f.read()
+            try:
+                jpeg_parse(data)
+                return jpeg_decode([data])
+            except JpegUnsupported as e:
+                why = str(e)
+        print(f"{image_path}: decoded by Pillow ({why})")
+    with Image.open(image_path) as im:
+        return np.asarray(im.convert("RGB"), np.uint8)[None]
 
 
 def main(argv=None):
@@ -62,24 +86,23 @@ def main(argv=None):
     denoiser = Denoiser(load_generator(model_path), tile=args.tile or None, margin=args.margin, pad=args.pad,
                         batch=args.batch)
     for image_path in image_paths:
-        with Image.open(image_path) as im:
-            noisy = np.asarray(im.convert("RGB"), np.uint8)
+        noisy = read_image(image_path, args.decode)
         if args.format == "jpg":
             from dgan.jpeg import jpeg_encode
-            frame = denoiser.run(noisy[None]).u8_out
+            frame = denoiser.run(noisy).u8_out
             if args.post == "median3":
                 from dgan.filters import median3
                 frame = median3(frame)
             out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
             with open(out_path, "wb") as f:
                 f.write(jpeg_encode(frame, args.jpeg_quality)[0])
-            print(f"{image_path} -> {out_path} {noisy.shape[1]}x{noisy.shape[0]}")
+            print(f"{image_path} -> {out_path} {noisy.shape[2]}x{noisy.shape[1]}")
             continue
         if args.post == "median3":
             from dgan.filters import median3
-            clean = median3(denoiser.run(noisy[None]).u8_out).cpu().numpy()[0]
+            clean = median3(denoiser.run(noisy).u8_out).cpu().numpy()[0]
         else:
-            clean = denoiser.denoise(noisy)
+            clean = denoiser.run(noisy).u8_out.cpu().numpy()[0]
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(clean, "RGB").save(out_path)
         print(f"{image_path} -> {out_path} {clean.shape[1]}x{clean.shape[0]}")

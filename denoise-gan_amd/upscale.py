@@ -12,7 +12,9 @@ and written with Pillow, as RGB, under their file names.  Whole images by defaul
 SRGAN's), --batch of them per forward.  --fp16 1 runs the 3x3 convs on the mixed_float16 policy;
 the fused FastSRGAN blocks stay fp32 (dgan/sr_infer.py).  --format jpg writes <stem>.jpg at
 --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and only the
-file's bytes are read back.
+file's bytes are read back.  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes and
+decodes them on the device (dgan.jpeg.jpeg_decode); every other file goes through Pillow, with a
+line that says why.
 """
 import os
 from argparse import ArgumentParser
@@ -33,6 +35,8 @@ parser.add_argument("--fp16", default=0, type=int, help="Run the conv GEMMs on t
 parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
                     help="keep: Pillow writes every image under its own name; jpg: baseline JPEG files encoded on the device.")
 parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
+parser.add_argument("--decode", default="pillow", choices=["pillow", "device"],
+                    help="device: baseline 4:2:0 .jpg / .jpeg files are decoded on the device; every other file through Pillow.")
 
 
 def load_network(arch, model_path, scale=4, fp16=False):
@@ -58,6 +62,7 @@ def load_network(arch, model_path, scale=4, fp16=False):
 def main(argv=None):
     from PIL import Image
     from dgan.sr_infer import Upscaler
+    from infer import read_image
     args = parser.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
@@ -70,17 +75,16 @@ def main(argv=None):
     upscaler = Upscaler(net, scale, multiple=multiple, tile=args.tile or None, margin=args.margin, pad=args.pad,
                         batch=args.batch)
     for image_path in image_paths:
-        with Image.open(image_path) as im:
-            low = np.asarray(im.convert("RGB"), np.uint8)
+        low = read_image(image_path, args.decode)
         if args.format == "jpg":
             from dgan.jpeg import jpeg_encode
-            frame = upscaler.run(low[None]).u8_out
+            frame = upscaler.run(low).u8_out
             out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
             with open(out_path, "wb") as f:
                 f.write(jpeg_encode(frame, args.jpeg_quality)[0])
             print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
             continue
-        high = upscaler.upscale(low)
+        high = upscaler.run(low).u8_out.cpu().numpy()[0]
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(high, "RGB").save(out_path)
         print(f"{image_path} -> {out_path} {high.shape[1]}x{high.shape[0]}")

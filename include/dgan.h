@@ -721,6 +721,38 @@ int dg_jpeg_encode_emit(int n, int h, int w, const void *ws, size_t ws_bytes, co
                         unsigned char *out, size_t out_stride, int *sizes, dg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Baseline JPEG decoder (dgan/jpeg.py jpeg_decode_ref: what libjpeg decodes from a baseline 4:2:0
+ * file with the "islow" IDCT and "fancy" upsampling).  n files of one size h x w -> dense RGB
+ * images [n][h][w][3]; integers only.  `blob`: DEVICE memory, 16-byte aligned, one upload from
+ * the host (dgan/jpeg.py _decode_blob; the layout: csrc/jpeg_dec.hip): per image a descriptor
+ * (scan offset and bytes, offset of its Huffman lookup tables, table selectors, quantisation
+ * tables), the table sets, the scans as they stand in the files.  max_scan_bytes: the longest
+ * scan of the call, below 2^28; it sizes the workspace (dg_jpeg_decode_ws_bytes, 16-byte aligned),
+ * which all calls of one decode share.  The workspace starts with one int32 at byte 0, the count
+ * of synchronisation rounds that changed a state so far, and n int32 status words from byte 16:
+ * 0, or bit 0: the scan holds fewer blocks than the image, bit 1: a symbol reached past the
+ * scan's end, bit 2: a descriptor points outside the blob.
+ * dg_jpeg_decode_scan    removes the byte stuffing and decodes every subsequence of
+ *     dg_jpeg_decode_geometry's bytes from its first bit, then synchronises the subsequences
+ *     inside every workgroup of `lanes` of them.
+ * dg_jpeg_decode_sync    round r >= 1 of the synchronisation across workgroups.  The caller reads
+ *     the counter after a round and stops when it has not moved, or after as many rounds as
+ *     an image has workgroups less one (ceil(ceil(max_scan_bytes / subsequence) / lanes) - 1);
+ *     a scan inside one workgroup needs none.  Nothing on the device waits for another workgroup.
+ * dg_jpeg_decode_pixels  block counts and their scan, the levels as int16 [n][block][64], the DC
+ *     sums, dequantisation, IDCT and range limit into the round trip's uint8 planes, then its
+ *     pixel kernel.  An image whose status is not 0 has unspecified pixels; no input makes a
+ *     kernel read or write outside the blob, the workspace and `out`. */
+int dg_jpeg_decode_geometry(int *subsequence_bytes, int *lanes);
+int dg_jpeg_decode_ws_bytes(int n, int h, int w, long long max_scan_bytes, size_t *bytes);
+int dg_jpeg_decode_scan(int n, int h, int w, const void *blob, size_t blob_bytes, long long max_scan_bytes, void *ws,
+                        size_t ws_bytes, dg_stream_t stream);
+int dg_jpeg_decode_sync(int n, int h, int w, const void *blob, size_t blob_bytes, long long max_scan_bytes, void *ws,
+                        size_t ws_bytes, int round, dg_stream_t stream);
+int dg_jpeg_decode_pixels(int n, int h, int w, const void *blob, size_t blob_bytes, long long max_scan_bytes, void *ws,
+                          size_t ws_bytes, unsigned char *out, dg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Classical filters (dgan/filters.py median3_ref / nlm_ref).  Dense RGB images [n][h][w][3] ->
  * the same shape, any byte alignment; integer arithmetic only, so the results equal the numpy
  * references bit for bit and two calls give the same bits.  One launch each, no workspace; `out`
