@@ -298,7 +298,10 @@ class SREvaluator:
     uploaded, degraded by a resize (dgan.resize, the degrade conversion) straight into the
     Upscaler frame's `u8_in`, upscaled into `u8_out`, and the same low-resolution frame resized
     back (the display conversion) is the baseline; both are scored against the original and only
-    the 4 n scalars come back.  `method` names the resize of both directions.  With a
+    the 4 n scalars come back.  `method` names the resize of both directions.  protocol "pil"
+    resizes both ways as Pillow's `Image.resize` does (dgan.resize.resize_pil with `filter`,
+    antialiased, no conversion: the usual way super-resolution scores are reported) instead of
+    the training pipeline's tf.image.resize of protocol "tf"; `method` is then unused.  With a
     graph-capturing `Upscaler` the resizes and the metrics run eagerly around the replay.
     jpeg_quality Q puts the low-resolution frame through a JPEG round trip at quality Q with 4:2:0
     subsampling (dataloader.jpeg_roundtrip on uint8), in place: codec "device" on the device
@@ -309,10 +312,17 @@ class SREvaluator:
 
     CODECS = ("device", "pillow")
 
-    def __init__(self, upscaler, method="bicubic", jpeg_quality=None, codec="device"):
-        from .resize import METHODS
+    PROTOCOLS = ("tf", "pil")
+
+    def __init__(self, upscaler, method="bicubic", jpeg_quality=None, codec="device", protocol="tf", filter="bicubic"):
+        from .resize import METHODS, PIL_FILTERS
+        if protocol not in self.PROTOCOLS:
+            raise ValueError(f"protocol must be one of {self.PROTOCOLS}, got {protocol!r}")
         if method not in METHODS:
             raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+        if filter not in PIL_FILTERS:
+            raise ValueError(f"filter must be one of {PIL_FILTERS}, got {filter!r}")
+        self.protocol, self.filter = protocol, filter
         if codec not in self.CODECS:
             raise ValueError(f"codec must be one of {self.CODECS}, got {codec!r}")
         if jpeg_quality is not None and not 1 <= int(jpeg_quality) <= 100:
@@ -353,7 +363,7 @@ class SREvaluator:
         -> {"psnr_bicubic", "psnr_upscaled", "ssim_bicubic", "ssim_upscaled"}: fp64 numpy arrays
         [n] (max_val 255)."""
         import torch
-        from .resize import DEGRADE, DISPLAY, resize
+        from .resize import DEGRADE, DISPLAY, resize, resize_pil
         hr = np.asarray(hr_u8)
         if hr.ndim == 3:
             hr = hr[None]
@@ -369,11 +379,17 @@ class SREvaluator:
         f = self.upscaler.frame(n, H // s, W // s)
         ref, base, res = self.buffers(tuple(hr.shape))
         ref.copy_(torch.from_numpy(np.ascontiguousarray(hr)))
-        resize(ref, H // s, W // s, self.method, *DEGRADE, out=f.u8_in)
+        if self.protocol == "pil":
+            resize_pil(ref, H // s, W // s, self.filter, out=f.u8_in)
+        else:
+            resize(ref, H // s, W // s, self.method, *DEGRADE, out=f.u8_in)
         if self.jpeg_quality is not None:
             self._jpeg(f.u8_in)
         self.upscaler.run_frame(f)
-        resize(f.u8_in, H, W, self.method, *DISPLAY, out=base)
+        if self.protocol == "pil":
+            resize_pil(f.u8_in, H, W, self.filter, out=base)
+        else:
+            resize(f.u8_in, H, W, self.method, *DISPLAY, out=base)
         psnr(base, ref, out=res[0])
         psnr(f.u8_out, ref, out=res[1])
         ssim(base, ref, out=res[2])

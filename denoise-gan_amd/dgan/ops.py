@@ -1228,6 +1228,43 @@ def resize(x, out, iy, wy, ix, wx, mul=1.0, bias=0.0):
     return out
 
 
+def resize_pil_tile(hi, wi, C, ho, wo, ksx, ksy):
+    """(th, tw, LDS bytes): the output tile dg_resize_pil_u8 takes for these sizes (host only);
+    DGError when a single output pixel does not fit a block's LDS."""
+    th, tw, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+    call("dg_resize_pil_tile", int(hi), int(wi), int(C), int(ho), int(wo), int(ksx), int(ksy), ctypes.byref(th),
+         ctypes.byref(tw), ctypes.byref(nb))
+    return th.value, tw.value, nb.value
+
+
+def resize_pil(x, out, tx, ty):
+    """out[n,ho,wo,C] = Pillow's resize (dg_resize_pil_u8) of the dense uint8 images x[n,hi,wi,C],
+    C 1 or 3; tx / ty: the device tables (first [n_out], count [n_out], k [n_out, ksize], int32)
+    of the horizontal / vertical pass (dgan.resize.pil_coeffs, or the identity)."""
+    for t in (x, out):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise DGError(f"resize_pil: expected uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+        if t.dim() != 4 or not t.is_contiguous():
+            raise DGError(f"resize_pil: expected dense [n,h,w,C] tensors, got shape {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise DGError("resize_pil: expected device tensors (the HIP path has no CPU fallback)")
+    n, hi, wi, C = x.shape
+    ho, wo = out.shape[1:3]
+    if out.shape[0] != n or out.shape[3] != C:
+        raise DGError(f"resize_pil: the output {tuple(out.shape)} does not match the input {tuple(x.shape)}")
+    ks = []
+    for (first, count, k), m, what in ((tx, wo, "x"), (ty, ho, "y")):
+        if k.dim() != 2 or k.shape[0] != m or k.shape[1] < 1:
+            raise DGError(f"resize_pil {what} k: expected [{m}, ksize], got {tuple(k.shape)}")
+        _metric_buf(first, torch.int32, m, f"resize_pil {what} first")
+        _metric_buf(count, torch.int32, m, f"resize_pil {what} count")
+        _metric_buf(k, torch.int32, m * k.shape[1], f"resize_pil {what} k")
+        ks.append(k.shape[1])
+    call("dg_resize_pil_u8", n, hi, wi, C, ho, wo, _p(x), _p(out), _p(tx[0]), _p(tx[1]), _p(tx[2]), ks[0], _p(ty[0]),
+         _p(ty[1]), _p(ty[2]), ks[1], _stream())
+    return out
+
+
 # ---- JPEG round trip (include/dgan.h "JPEG round trip") -------------------------------------------
 def jpeg_workspace_bytes(n, h, w):
     nb = ctypes.c_size_t()

@@ -21,8 +21,16 @@ weights are dyadic, v * mul + bias is then an exact integer on about 5 % of the 
 within 4e-14 of one beside the renormalised edge taps, so another summation order or a contracted
 FMA flips pixels.  With the order fixed the device output equals `resize_ref` bit for bit.
 
-`resize_taps` / `resize_ref` are pure numpy and import neither torch nor the library.
+A second convention, Pillow's `Image.resize` (antialiased: the filter's support grows with the
+downscale factor; 8-bit fixed point, horizontal pass first, the intermediate rounded to uint8):
+`pil_coeffs` / `resize_pil_ref` / `resize_pil` (csrc/resize_pil.hip), integers once the coefficients
+exist and equal to Pillow bit for bit.  It shares nothing with the first but the plan cache.
+
+`resize_taps` / `resize_ref` / `pil_coeffs` / `resize_pil_ref` are pure numpy and import neither
+torch nor the library.
 """
+import math
+
 import numpy as np
 
 METHODS = ("bicubic", "bilinear")
@@ -108,6 +116,123 @@ def resize_ref(img, h, w, method="bicubic", mul=1.0, bias=0.0):
 
 
 # ---------------------------------------------------------------------------
+# Pillow's Image.resize: antialiased, 8-bit fixed point.  The filter's support grows with the
+# downscale factor; the coefficients are fp64 once, integers from then on (Resample.c).
+# ---------------------------------------------------------------------------
+PIL_FILTERS = ("box", "bilinear", "hamming", "bicubic", "lanczos")
+_PIL_SUPPORT = {"box": 0.5, "bilinear": 1.0, "hamming": 1.0, "bicubic": 2.0, "lanczos": 3.0}
+PIL_BITS = 22   # fraction bits of a coefficient (Resample.c PRECISION_BITS = 32 - 8 - 2)
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _pil_filter(name, x):
+    """Pillow's filter kernels at the scalar x, in its order of operations."""
+    if name == "box":
+        return 1.0 if -0.5 < x <= 0.5 else 0.0
+    if name == "lanczos":
+        return _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0
+    x = abs(x)
+    if name == "bilinear":
+        return 1.0 - x if x < 1.0 else 0.0
+    if name == "hamming":
+        if x == 0.0:
+            return 1.0
+        if x >= 1.0:
+            return 0.0
+        x = x * math.pi
+        return math.sin(x) / x * (0.54 + 0.46 * math.cos(x))
+    a = -0.5
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def pil_coeffs(n_in, n_out, filter="bicubic"):
+    """(first int32 [n_out], count int32 [n_out], k int32 [n_out, ksize]) of one axis: output o is
+    clip((2^21 + sum_{j < count[o]} k[o,j] * in[first[o] + j]) >> 22, 0, 255).  fp64 in Pillow's
+    order (precompute_coeffs, normalize_coeffs_8bpc); entries of k beyond count are 0."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"pil_coeffs: sizes must be at least 1, got {n_in} -> {n_out}")
+    if filter not in PIL_FILTERS:
+        raise ValueError(f"pil_coeffs: filter must be one of {PIL_FILTERS}, got {filter!r}")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = _PIL_SUPPORT[filter] * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    first = np.zeros(n_out, np.int32)
+    count = np.zeros(n_out, np.int32)
+    k = np.zeros((n_out, ksize), np.int32)
+    for o in range(n_out):
+        center = (o + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        cnt = min(int(center + support + 0.5), n_in) - lo
+        w = [_pil_filter(filter, (j + lo - center + 0.5) / fs) for j in range(cnt)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        first[o], count[o] = lo, cnt
+        k[o, :cnt] = [int(v * (1 << PIL_BITS) - 0.5) if v < 0 else int(v * (1 << PIL_BITS) + 0.5) for v in w]
+    return first, count, k
+
+
+def _pil_pass(a, axis, first, count, k, dtype):
+    """One fixed-point pass along `axis` of the uint8 array a -> uint8."""
+    a = np.moveaxis(a, axis, -1).astype(dtype)
+    out = np.empty(a.shape[:-1] + (len(first),), np.uint8)
+    half = dtype(1 << (PIL_BITS - 1))
+    for o in range(len(first)):
+        s = (a[..., first[o]:first[o] + count[o]] * k[o, :count[o]].astype(dtype)).sum(-1, dtype=dtype) + half
+        out[..., o] = np.clip(s >> PIL_BITS, 0, 255)
+    return np.moveaxis(out, -1, axis)
+
+
+def resize_pil_ref(img, h, w, filter="bicubic", dtype=np.int64):
+    """Pillow's `Image.resize((w, h), filter)` on the host: uint8 [n,hi,wi,C] or [hi,wi,C] -> uint8
+    at h x w.  The horizontal pass runs first (if w != wi), the vertical pass on its uint8 result
+    (if h != hi); a same-size call is a copy.  dtype: the working integer type, np.int64 or
+    np.int32; they give the same bits, since |2^21 + sum k * in| <= 2^21 + 255 * sum |k| stays
+    below 2^31 while sum |k| < 2.006 * 2^22, and a normalised window has sum |k| = (1 + 2 m) * 2^22
+    up to rounding with m the weight of its negative lobes: none for box, bilinear and hamming,
+    at most 0.14 for bicubic and 0.28 for lanczos, windows cut by the image's edge included
+    (sum |k| <= 1.27 and 1.55 times 2^22; tests/test_resize_pil.py asserts the bound itself).
+
+    Equal to Pillow bit for bit wherever it was compared (tests/test_resize_pil.py).  For box,
+    bilinear and bicubic the coefficients are fp64 +, *, / only; those of lanczos and hamming go
+    through libm's sin / cos on the host, so for these two the equality is an observation on the
+    machines it was run on, not a theorem.  The device never evaluates a filter."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim not in (3, 4):
+        raise ValueError(f"resize_pil_ref: expected uint8 [n,h,w,C] or [h,w,C], got {a.dtype} {a.shape}")
+    if dtype not in (np.int64, np.int32):
+        raise ValueError(f"resize_pil_ref: dtype must be np.int64 or np.int32, got {dtype}")
+    if filter not in PIL_FILTERS:
+        raise ValueError(f"resize_pil_ref: filter must be one of {PIL_FILTERS}, got {filter!r}")
+    h, w = int(h), int(w)
+    single = a.ndim == 3
+    if single:
+        a = a[None]
+    if min(h, w) < 1 or min(a.shape[1:]) < 1:
+        raise ValueError(f"resize_pil_ref: empty image: {a.shape} -> {h}x{w}")
+    if w != a.shape[2]:
+        a = _pil_pass(a, 2, *pil_coeffs(a.shape[2], w, filter), dtype)
+    if h != a.shape[1]:
+        a = _pil_pass(a, 1, *pil_coeffs(a.shape[1], h, filter), dtype)
+    out = np.array(a, np.uint8)
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
 # device code below: torch and the library are imported on use
 # ---------------------------------------------------------------------------
 class _Plan:
@@ -163,3 +288,77 @@ def resize(x, h, w, method="bicubic", mul=1.0, bias=0.0, out=None):
     if n and out.data_ptr() == x.data_ptr():
         raise ValueError("resize: out must not be the input")
     return ops.resize(x, out, p.iy, p.wy, p.ix, p.wx, mul, bias)
+
+
+def _pil_identity(n):
+    """The tables of an axis that keeps its size: one tap of weight 1, so the pass is a copy."""
+    return np.arange(n, dtype=np.int32), np.ones(n, np.int32), np.full((n, 1), 1 << PIL_BITS, np.int32)
+
+
+def pil_ksize(n_in, n_out, filter):
+    """Taps per output of one axis: pil_coeffs' ksize, 1 for an axis that keeps its size."""
+    if n_in == n_out:
+        return 1
+    return int(math.ceil(_PIL_SUPPORT[filter] * max(n_in / n_out, 1.0))) * 2 + 1
+
+
+def pil_tile(hi, wi, h, w, filter="bicubic", C=3):
+    """(th, tw, LDS bytes): the output tile of the kernel for these sizes (host only); ValueError
+    when the downscale is steeper than a block's LDS holds."""
+    from . import ops
+    try:
+        return ops.resize_pil_tile(hi, wi, C, h, w, pil_ksize(wi, w, filter), pil_ksize(hi, h, filter))
+    except ops.DGError as e:
+        raise ValueError(f"resize_pil: {hi}x{wi} -> {h}x{w} is too steep a downscale: {e}") from None
+
+
+class _PilPlan:
+    """The device coefficient tables of one (hi, wi, h, w, filter, device) and the output buffer of
+    the last (n, C) seen on it."""
+
+    def __init__(self, hi, wi, h, w, filter, device):
+        import torch
+        tabs = [pil_coeffs(n_in, n_out, filter) if n_in != n_out else _pil_identity(n_out)
+                for n_in, n_out in ((wi, w), (hi, h))]
+        self.tx, self.ty = (tuple(torch.from_numpy(t).to(device) for t in tab) for tab in tabs)
+        self.out = None
+
+
+def resize_pil(x, h, w, filter="bicubic", out=None):
+    """A dense uint8 NHWC device tensor [n,hi,wi,C], C 1 or 3 -> uint8 [n,h,w,C], equal to
+    `resize_pil_ref` (Pillow's `Image.resize((w, h), filter)`) bit for bit.  Four channels are
+    refused: Pillow premultiplies RGBA by alpha.  The result is `out` or the plan's own buffer,
+    which the next call on the same sizes and filter overwrites; a repeated call allocates nothing.
+    One launch, no host sync, no atomics: it can be captured in a graph."""
+    import torch
+    from . import ops
+    from .metrics import _lru
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise ValueError(f"resize_pil: expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 4 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError(f"resize_pil: expected a dense [n,h,w,C] device tensor, got shape {tuple(x.shape)} on {x.device}")
+    if filter not in PIL_FILTERS:
+        raise ValueError(f"resize_pil: filter must be one of {PIL_FILTERS}, got {filter!r}")
+    h, w = int(h), int(w)
+    n, hi, wi, C = x.shape
+    if min(h, w, hi, wi) < 1:
+        raise ValueError(f"resize_pil: empty image: {tuple(x.shape)} -> {h}x{w}")
+    if C not in (1, 3):
+        raise ValueError(f"resize_pil: C must be 1 or 3 (Pillow premultiplies a fourth channel), got {C}")
+    key = (hi, wi, h, w, "pil:" + filter, x.device)
+    pil_tile(hi, wi, h, w, filter, C)   # (a host call: refuses a factor the kernel cannot take, by name)
+    p = _lru(_plans, key, lambda: _PilPlan(hi, wi, h, w, filter, x.device), MAX_PLANS)
+    shape = (n, h, w, C)
+    if out is None:
+        if p.out is None or tuple(p.out.shape) != shape:
+            p.out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        out = p.out
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape
+          or not out.is_contiguous() or out.device != x.device):
+        raise ValueError(f"resize_pil: out must be a dense uint8 {shape} tensor on {x.device}, got "
+                         f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+    if n and out.data_ptr() == x.data_ptr():
+        raise ValueError("resize_pil: out must not be the input")
+    if n == 0:
+        return out
+    return ops.resize_pil(x, out, p.tx, p.ty)

@@ -12,6 +12,10 @@ ssim_bicubic, ssim_upscaled.  An image whose sides are not multiples of the scal
 to the largest multiple (the crop is printed); one with a side below the 11x11 SSIM window after the
 crop is refused by name.  The metrics are the tf.image.psnr / tf.image.ssim defaults on uint8 RGB
 (max_val 255), accumulated in fp64.
+
+--protocol pil degrades and upscales the baseline as Pillow's `Image.resize` does instead
+(dgan.resize.resize_pil with --filter, antialiased: how super-resolution scores are usually
+reported); the JSON names the protocol used.
 """
 import json
 import os
@@ -32,6 +36,10 @@ parser.add_argument("--margin", default=0, type=int, help="Context pixels on eac
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
 parser.add_argument("--jpeg_quality", default=0, type=int, help="JPEG quality of the low-resolution frame (0: no JPEG step).")
+parser.add_argument("--protocol", default="tf", choices=["tf", "pil"],
+                    help="tf: the training pipeline's tf.image.resize; pil: Pillow's Image.resize, antialiased.")
+parser.add_argument("--filter", default="bicubic", choices=["box", "bilinear", "hamming", "bicubic", "lanczos"],
+                    help="The filter of --protocol pil.")
 parser.add_argument("--json", default=None, type=str, help="Also write the scores and their means to this file.")
 
 
@@ -54,7 +62,8 @@ def main(argv=None):
     model_path = os.path.expanduser(os.path.expandvars(args.model))
     net, scale, multiple = load_network(args.arch, model_path, args.scale, bool(args.fp16))
     evaluator = metrics.SREvaluator(Upscaler(net, scale, multiple=multiple, tile=args.tile or None, margin=args.margin,
-                                             pad=args.pad, batch=args.batch), jpeg_quality=args.jpeg_quality or None)
+                                             pad=args.pad, batch=args.batch), jpeg_quality=args.jpeg_quality or None,
+                                    protocol=args.protocol, filter=args.filter)
     rows = []
     for name in sorted(os.listdir(image_dir)):
         hr, box = centre_crop(_read_rgb(os.path.join(image_dir, name)), scale)
@@ -68,6 +77,7 @@ def main(argv=None):
         rows.append({"name": name, **row})
         print(name + "".join(f" {k} {v:.4f}" for k, v in row.items()))
     result = summarize(rows)
+    result["protocol"] = args.protocol if args.protocol == "tf" else f"pil:{args.filter}"
     print("mean" + "".join(f" {k} {v:.4f}" for k, v in result["mean"].items()) + f" ({len(rows)} images)")
     if args.json:
         with open(os.path.expanduser(os.path.expandvars(args.json)), "w") as f:

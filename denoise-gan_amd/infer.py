@@ -12,7 +12,8 @@ with --margin M runs T x T tiles with M pixels of context instead, --batch of th
 <stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
 only the file's bytes are read back.  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
 and decodes them on the device (dgan.jpeg.jpeg_decode); every other file goes through Pillow, with
-a line that says why.
+a line that says why.  --resize WxH [--resize_filter lanczos] resizes the output frame on the
+device as Pillow's `Image.resize` does (dgan.resize.resize_pil) before it is read back or encoded.
 
 Deviation from the reference: the generator is fed [-1, 1] (uint8 / 255 * 2 - 1, what it was
 trained on, dataloader.py:173-175); the reference's infer.py:55 feeds [0, 1].
@@ -38,6 +39,10 @@ parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
 parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
 parser.add_argument("--decode", default="pillow", choices=["pillow", "device"],
                     help="device: baseline 4:2:0 .jpg / .jpeg files are decoded on the device; every other file through Pillow.")
+parser.add_argument("--resize", default=None, type=str,
+                    help="WxH: resize the output frame on the device, as Pillow's Image.resize does, before it is written.")
+parser.add_argument("--resize_filter", default="bicubic", choices=["box", "bilinear", "hamming", "bicubic", "lanczos"],
+                    help="The filter of --resize.")
 
 
 def load_generator(model_path):
@@ -72,12 +77,34 @@ def read_image(image_path, decode):
         return np.asarray(im.convert("RGB"), np.uint8)[None]
 
 
+def parse_size(text):
+    """'WxH' -> (W, H), both at least 1; None for None."""
+    if text is None:
+        return None
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        w = h = 0
+    if min(w, h) < 1:
+        parser.error(f"--resize expects WxH with both at least 1, got {text!r}")
+    return w, h
+
+
+def resized(frame, size, filter):
+    """The device frame [1,h,w,3] at `size` = (W, H) (dgan.resize.resize_pil), or itself for None."""
+    if size is None:
+        return frame
+    from dgan.resize import resize_pil
+    return resize_pil(frame.contiguous(), size[1], size[0], filter)
+
+
 def main(argv=None):
     from PIL import Image
     from dgan.infer import Denoiser
     args = parser.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
+    size = parse_size(args.resize)
     image_dir = os.path.expanduser(os.path.expandvars(args.image_dir))
     output_dir = os.path.expanduser(os.path.expandvars(args.output_dir))
     model_path = os.path.expanduser(os.path.expandvars(args.model))
@@ -93,16 +120,17 @@ def main(argv=None):
             if args.post == "median3":
                 from dgan.filters import median3
                 frame = median3(frame)
+            frame = resized(frame, size, args.resize_filter)
             out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
             with open(out_path, "wb") as f:
                 f.write(jpeg_encode(frame, args.jpeg_quality)[0])
-            print(f"{image_path} -> {out_path} {noisy.shape[2]}x{noisy.shape[1]}")
+            print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
             continue
+        frame = denoiser.run(noisy).u8_out
         if args.post == "median3":
             from dgan.filters import median3
-            clean = median3(denoiser.run(noisy).u8_out).cpu().numpy()[0]
-        else:
-            clean = denoiser.run(noisy).u8_out.cpu().numpy()[0]
+            frame = median3(frame)
+        clean = resized(frame, size, args.resize_filter).cpu().numpy()[0]
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(clean, "RGB").save(out_path)
         print(f"{image_path} -> {out_path} {clean.shape[1]}x{clean.shape[0]}")

@@ -14,7 +14,8 @@ the fused FastSRGAN blocks stay fp32 (dgan/sr_infer.py).  --format jpg writes <s
 --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and only the
 file's bytes are read back.  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes and
 decodes them on the device (dgan.jpeg.jpeg_decode); every other file goes through Pillow, with a
-line that says why.
+line that says why.  --resize WxH [--resize_filter lanczos] resizes the upscaled frame on the
+device as Pillow's `Image.resize` does (dgan.resize.resize_pil) before it is read back or encoded.
 """
 import os
 from argparse import ArgumentParser
@@ -37,6 +38,10 @@ parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
 parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
 parser.add_argument("--decode", default="pillow", choices=["pillow", "device"],
                     help="device: baseline 4:2:0 .jpg / .jpeg files are decoded on the device; every other file through Pillow.")
+parser.add_argument("--resize", default=None, type=str,
+                    help="WxH: resize the output frame on the device, as Pillow's Image.resize does, before it is written.")
+parser.add_argument("--resize_filter", default="bicubic", choices=["box", "bilinear", "hamming", "bicubic", "lanczos"],
+                    help="The filter of --resize.")
 
 
 def load_network(arch, model_path, scale=4, fp16=False):
@@ -62,8 +67,9 @@ def load_network(arch, model_path, scale=4, fp16=False):
 def main(argv=None):
     from PIL import Image
     from dgan.sr_infer import Upscaler
-    from infer import read_image
+    from infer import parse_size, read_image, resized
     args = parser.parse_args(argv)
+    size = parse_size(args.resize)
     if not 1 <= args.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
     image_dir = os.path.expanduser(os.path.expandvars(args.image_dir))
@@ -78,13 +84,13 @@ def main(argv=None):
         low = read_image(image_path, args.decode)
         if args.format == "jpg":
             from dgan.jpeg import jpeg_encode
-            frame = upscaler.run(low).u8_out
+            frame = resized(upscaler.run(low).u8_out, size, args.resize_filter)
             out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
             with open(out_path, "wb") as f:
                 f.write(jpeg_encode(frame, args.jpeg_quality)[0])
             print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
             continue
-        high = upscaler.run(low).u8_out.cpu().numpy()[0]
+        high = resized(upscaler.run(low).u8_out, size, args.resize_filter).cpu().numpy()[0]
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(high, "RGB").save(out_path)
         print(f"{image_path} -> {out_path} {high.shape[1]}x{high.shape[0]}")

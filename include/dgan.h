@@ -680,6 +680,24 @@ int dg_resize_f32(int n, int hi, int wi, int C, int ho, int wo, const float *in,
                   const double *wy, const int *ix, const double *wx, dg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * Image resize, Pillow's (dgan/resize.py pil_coeffs / resize_pil_ref: `Image.resize`, antialiased,
+ * 8-bit fixed point).  Dense uint8 NHWC images [n][hi][wi][C] -> [n][ho][wo][C], C 1 or 3, any byte
+ * alignment.  Per axis three device tables: first [n_out], count [n_out] and k [n_out][ksize] (int32,
+ * |k| < 2^23, 22 fraction bits); one pass is
+ *   out[o] = clip((2^21 + sum_{j < count[o]} k[o][j] * in[first[o] + j]) >> 22, 0, 255),
+ * the horizontal pass (fx, cx, kx, ksx) first, the vertical one (fy, cy, ky, ksy) on its uint8
+ * result; an axis that keeps its size takes the identity tables (first o, count 1, k 2^22).
+ * Integers only, one launch, no workspace and no atomics: a block keeps the intermediate rows of
+ * its output tile in LDS.  The kernel clamps first and count into the image.  `in` and `out`
+ * must not be the same buffer.  dg_resize_pil_tile: the output tile (th x tw pixels) and the LDS
+ * bytes of a block that dg_resize_pil_u8 takes for these sizes (host only); both return DG_ERR_ARG
+ * when the rows and coefficients of a single output pixel do not fit a block's 64 KB of LDS. */
+int dg_resize_pil_tile(int hi, int wi, int C, int ho, int wo, int ksx, int ksy, int *th, int *tw, size_t *lds_bytes);
+int dg_resize_pil_u8(int n, int hi, int wi, int C, int ho, int wo, const unsigned char *in, unsigned char *out,
+                     const int *fx, const int *cx, const int *kx, int ksx, const int *fy, const int *cy, const int *ky,
+                     int ksy, dg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * JPEG round trip (dgan/jpeg.py jpeg_ref: libjpeg's compress + decompress at 4:2:0 with the
  * "islow" DCTs and "fancy" upsampling, minus the lossless entropy coder).  Dense RGB images
  * [n][h][w][3] -> the same shape, any byte alignment; int32 arithmetic only, so the result equals
