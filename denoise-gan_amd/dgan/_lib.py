@@ -173,6 +173,10 @@ _SIGS = {
     "dg_jpeg_decode_scan": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, _P]),
     "dg_jpeg_decode_sync": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, c_int, _P]),
     "dg_jpeg_decode_pixels": (c_int, [c_int] * 3 + [_P, c_size_t, c_int64, _P, c_size_t, _P, _P]),
+    "dg_png_encode_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "dg_png_encode": (c_int, [c_int] * 3 + [_P, c_void_p, c_int, _P, c_size_t, _P, c_size_t, _P, _P]),
+    "dg_png_deflate_bytes": (c_int, [c_int, c_int64, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]),
+    "dg_png_deflate": (c_int, [c_int, c_int64, _P, _P, c_size_t, _P, c_size_t, _P, _P]),
     "dg_median3_u8": (c_int, [c_int] * 3 + [_P, _P, _P]),
     "dg_nlm_u8": (c_int, [c_int] * 5 + [_P, c_int, _P, _P, _P]),
 }

@@ -1367,6 +1367,70 @@ def jpeg_encode_emit(shape, ws, bits, max_bits, header, stream_ws, out, sizes):
     return sizes
 
 
+# ---- PNG encoder (include/dgan.h "PNG encoder") ---------------------------------------------------
+def png_encode_bytes(n, h, w):
+    """-> (bytes of the workspace, bytes between two files of `out`) of png_encode."""
+    ws, stride = ctypes.c_size_t(), ctypes.c_size_t()
+    call("dg_png_encode_bytes", int(n), int(h), int(w), ctypes.byref(ws), ctypes.byref(stride))
+    return ws.value, stride.value
+
+
+def _png_out(ws, out, sizes, n, need_ws, need_stride, like, what):
+    _jpeg_buf(ws, torch.uint8, need_ws, like, f"{what} ws")
+    _jpeg_buf(sizes, torch.int32, n, like, f"{what} sizes")
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or not out.is_contiguous()
+            or out.device != like.device or out.shape[0] != n or out.shape[1] < need_stride):
+        raise DGError(f"{what} out: expected a dense uint8 [{n}, >= {need_stride}] buffer on {like.device}")
+
+
+def png_encode(x, header, ws, out, sizes):
+    """The PNG files (dg_png_encode) of the dense uint8 images x[n,h,w,3]: out[i, :sizes[i]] is image
+    i's.  header: the host bytes of dgan.png.png_header; ws (uint8) and out (uint8 [n,stride]) sized by
+    png_encode_bytes, sizes int32 [n]."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise DGError(f"png_encode: expected a uint8 tensor, got {getattr(x, 'dtype', type(x))}")
+    if x.dim() != 4 or not x.is_contiguous() or x.shape[3] != 3:
+        raise DGError(f"png_encode: expected dense [n,h,w,3] tensors, got shape {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise DGError("png_encode: expected device tensors (the HIP path has no CPU fallback)")
+    n, h, w, _ = x.shape
+    header = bytes(header)
+    need_ws, need_stride = png_encode_bytes(n, h, w)
+    if n:
+        _png_out(ws, out, sizes, n, need_ws, need_stride, x, "png_encode")
+    hdr = (ctypes.c_ubyte * max(len(header), 1)).from_buffer_copy(header or b"\0")
+    call("dg_png_encode", n, h, w, _p(x), hdr, len(header), _p(ws) if n else None, ws.numel() if n else 0,
+         _p(out) if n else None, out.shape[1] if n else 0, _p(sizes) if n else None, _stream())
+    return sizes
+
+
+def png_deflate_bytes(n, length):
+    """-> (bytes of the workspace, bytes between two streams of `out`) of png_deflate."""
+    ws, stride = ctypes.c_size_t(), ctypes.c_size_t()
+    call("dg_png_deflate_bytes", int(n), int(length), ctypes.byref(ws), ctypes.byref(stride))
+    return ws.value, stride.value
+
+
+def png_deflate(data):
+    """The deflate stage of the PNG encoder on its own (dg_png_deflate): a dense uint8 device tensor
+    [n,len] -> (out uint8 [n,stride], sizes int32 [n]) on the device, out[i, :sizes[i]] the zlib
+    stream of row i as dgan.png.deflate_ref writes it.  Allocates its buffers; does not wait."""
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 2 or not data.is_contiguous():
+        raise DGError(f"png_deflate: expected a dense uint8 [n,len] tensor, got {getattr(data, 'dtype', type(data))} "
+                      f"{tuple(getattr(data, 'shape', ()))}")
+    if not data.is_cuda:
+        raise DGError("png_deflate: expected a device tensor (the HIP path has no CPU fallback)")
+    n, length = data.shape
+    need_ws, stride = png_deflate_bytes(n, length)
+    ws = torch.empty(max(need_ws, 16), dtype=torch.uint8, device=data.device)
+    out = torch.empty((n, stride), dtype=torch.uint8, device=data.device)
+    sizes = torch.empty(n, dtype=torch.int32, device=data.device)
+    if n:
+        call("dg_png_deflate", n, length, _p(data) if length else None, _p(ws), ws.numel(), _p(out), stride, _p(sizes),
+             _stream())
+    return out, sizes
+
+
 # ---- JPEG decoder (include/dgan.h "Baseline JPEG decoder") ----------------------------------------
 def jpeg_decode_geometry():
     """-> (bytes of a subsequence, subsequences of a workgroup) of the entropy decoder."""

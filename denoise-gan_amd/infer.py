@@ -10,7 +10,8 @@ with --margin M runs T x T tiles with M pixels of context instead, --batch of th
 --post median3 puts the denoised frame through a 3x3 median on the device before it is read back
 (dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).  --format jpg writes
 <stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
-only the file's bytes are read back.  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
+only the file's bytes are read back; --format png writes <stem>.png the same way, lossless
+(dgan.png.png_encode).  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
 and decodes them on the device (dgan.jpeg.jpeg_decode); every other file goes through Pillow, with
 a line that says why.  --resize WxH [--resize_filter lanczos] resizes the output frame on the
 device as Pillow's `Image.resize` does (dgan.resize.resize_pil) before it is read back or encoded.
@@ -34,8 +35,9 @@ parser.add_argument("--pad", default="black", choices=["black", "reflect"], help
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
 parser.add_argument("--post", default=None, choices=["median3"],
                     help="A classical filter applied to the denoised image on the device (default: none).")
-parser.add_argument("--format", default="keep", choices=["keep", "jpg"],
-                    help="keep: Pillow writes every image under its own name; jpg: baseline JPEG files encoded on the device.")
+parser.add_argument("--format", default="keep", choices=["keep", "jpg", "png"],
+                    help="keep: Pillow writes every image under its own name; jpg / png: baseline JPEG or PNG files "
+                         "encoded on the device.")
 parser.add_argument("--jpeg_quality", default=90, type=int, help="Quality of --format jpg (1..100).")
 parser.add_argument("--decode", default="pillow", choices=["pillow", "device"],
                     help="device: baseline 4:2:0 .jpg / .jpeg files are decoded on the device; every other file through Pillow.")
@@ -114,16 +116,21 @@ def main(argv=None):
                         batch=args.batch)
     for image_path in image_paths:
         noisy = read_image(image_path, args.decode)
-        if args.format == "jpg":
-            from dgan.jpeg import jpeg_encode
+        if args.format != "keep":
             frame = denoiser.run(noisy).u8_out
             if args.post == "median3":
                 from dgan.filters import median3
                 frame = median3(frame)
             frame = resized(frame, size, args.resize_filter)
-            out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + ".jpg")
+            out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + "." + args.format)
+            if args.format == "jpg":
+                from dgan.jpeg import jpeg_encode
+                data = jpeg_encode(frame, args.jpeg_quality)[0]
+            else:
+                from dgan.png import png_encode
+                data = png_encode(frame)[0]
             with open(out_path, "wb") as f:
-                f.write(jpeg_encode(frame, args.jpeg_quality)[0])
+                f.write(data)
             print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
             continue
         frame = denoiser.run(noisy).u8_out

@@ -771,6 +771,26 @@ int dg_jpeg_decode_pixels(int n, int h, int w, const void *blob, size_t blob_byt
                           size_t ws_bytes, unsigned char *out, dg_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * PNG encoder (dgan/png.py png_encode_ref, whose module docstring fixes the file: per-row filter by
+ * libpng's heuristic, a zlib stream of independent dynamic-Huffman blocks of 32768 stream bytes with
+ * matches at distance 1 only, one IDAT chunk per block).  Integers only, no read-back inside a call.
+ * dg_png_encode   dense RGB images [n][h][w][3], any byte alignment, h and w in 1..65535 and files
+ *     below 2^31 bytes -> every image's file at out + i * out_stride; sizes: n DEVICE int32, the
+ *     file lengths.  header: the 33 HOST bytes of signature and IHDR (dgan/png.py png_header).
+ *     Four launches: filter, blocks, scan, pack.
+ * dg_png_deflate  the last three alone: n dense byte streams [n][len], len >= 0 -> the zlib stream of
+ *     each (dgan/png.py deflate_ref) at out + i * out_stride, their lengths in sizes.
+ * ws (16-byte aligned) and out_stride are sized by dg_png_encode_bytes / dg_png_deflate_bytes for the
+ * same shape; out_stride is the longest file the shape can give (every block stored), so no call
+ * sizes a buffer from a device result. */
+int dg_png_encode_bytes(int n, int h, int w, size_t *ws_bytes, size_t *out_stride);
+int dg_png_encode(int n, int h, int w, const unsigned char *in, const unsigned char *header, int header_bytes, void *ws,
+                  size_t ws_bytes, unsigned char *out, size_t out_stride, int *sizes, dg_stream_t stream);
+int dg_png_deflate_bytes(int n, long long len, size_t *ws_bytes, size_t *out_stride);
+int dg_png_deflate(int n, long long len, const unsigned char *data, void *ws, size_t ws_bytes, unsigned char *out,
+                   size_t out_stride, int *sizes, dg_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * Classical filters (dgan/filters.py median3_ref / nlm_ref).  Dense RGB images [n][h][w][3] ->
  * the same shape, any byte alignment; integer arithmetic only, so the results equal the numpy
  * references bit for bit and two calls give the same bits.  One launch each, no workspace; `out`
