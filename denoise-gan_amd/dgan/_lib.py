@@ -179,6 +179,8 @@ _SIGS = {
     "dg_png_deflate": (c_int, [c_int, c_int64, _P, _P, c_size_t, _P, c_size_t, _P, _P]),
     "dg_median3_u8": (c_int, [c_int] * 3 + [_P, _P, _P]),
     "dg_nlm_u8": (c_int, [c_int] * 5 + [_P, c_int, _P, _P, _P]),
+    "dg_bm3d_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
+    "dg_bm3d_u8": (c_int, [c_int] * 6 + [_P, _P, c_size_t, _P, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

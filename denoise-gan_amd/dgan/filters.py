@@ -18,12 +18,20 @@ post-filter (infer.py --post median3).
                D < 2^24, S <= 441 * 2^14 and sum w v < 2^31: everything fits int32 (`nlm_ref` takes
                the working type as an argument; tests/test_filters.py holds int32 equal to int64).
 
+    bm3d       stage 1 (hard thresholding) of BM3D with the unnormalised Walsh-Hadamard transform in
+               all three dimensions: `bm3d_ref` states it in full.
+
 `nlm` is the non-local means of Buades et al. with one weight for the three channels.  It is NOT
 claimed equal to cv2.fastNlMeansDenoisingColored, which filters in Lab with separate luminance and
 colour strengths and its own fixed-point weights.
 
-`median3_ref` / `nlm_table` / `nlm_ref` are pure numpy and import neither torch nor the library.
+`bm3d` is BM3D (Dabov et al.) with a Hadamard transform, a known cheap variant.  It is NOT the
+Bior / DCT profile of the original paper and is not claimed equal to any other implementation.
+
+`median3_ref` / `nlm_table` / `nlm_ref` / `bm3d_ref` are pure numpy and import neither torch nor the library.
 """
+import math
+
 import numpy as np
 
 TEMPLATES = (3, 5, 7)
@@ -106,9 +114,139 @@ def nlm_ref(img_u8, h=10, template=7, search=21, dtype=np.int64):
 
 
 # ---------------------------------------------------------------------------
+# BM3D, stage 1
+# ---------------------------------------------------------------------------
+PATCH = 8                 # the patch is 8 x 8
+STEP = 3                  # reference patches every 3 pixels, from -7
+MAX_SIGMA = 40
+GROUPS = (2, 4, 8, 16)    # K: the most patches of a group
+MATCH_BOUND = 480000      # a candidate matches when D <= 2500 per sample * 192 samples
+ESTIMATE_MAX = 1020       # an estimate carries two fraction bits
+WEIGHT_SCALE = 1024       # w = max(1, 1024 // N)
+_NO_KEY = (1 << 31) - 1   # the sort key of a candidate that does not match
+
+
+def check_bm3d(sigma, search, group, what="bm3d"):
+    """(sigma, search, group) as ints, or ValueError naming the bad one."""
+    for name, v in (("sigma", sigma), ("search", search), ("group", group)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
+    if not 1 <= sigma <= MAX_SIGMA:
+        raise ValueError(f"{what}: sigma must be in 1..{MAX_SIGMA}, got {sigma}")
+    if not 3 <= search <= MAX_SEARCH or search % 2 == 0:
+        raise ValueError(f"{what}: search must be odd in 3..{MAX_SEARCH}, got {search}")
+    if group not in GROUPS:
+        raise ValueError(f"{what}: group must be one of {GROUPS}, got {group}")
+    return int(sigma), int(search), int(group)
+
+
+def hadamard(n):
+    """int64 [n,n]: the unnormalised Walsh-Hadamard matrix in Sylvester order, n a power of two."""
+    H = np.ones((1, 1), np.int64)
+    while len(H) < n:
+        H = np.block([[H, H], [H, -H]])
+    return H
+
+
+def bm3d_threshold(sigma, m):
+    """T(sigma, m) = isqrt(729 sigma^2 64 m // 100): 2.7 sigma on the scale of the unnormalised
+    transform of m x 8 x 8 values, whose coefficients carry a gain of sqrt(64 m)."""
+    return math.isqrt(729 * sigma * sigma * PATCH * PATCH * m // 100)
+
+
+def _wht3(G, Hm, H8):
+    """The transform of [g,m,8,8,3] along the group, the rows and the columns."""
+    G = np.einsum("ab,gbijc->gaijc", Hm, G)
+    G = np.einsum("ab,gkbjc->gkajc", H8, G)
+    return np.einsum("ab,gkibc->gkiac", H8, G)
+
+
+def bm3d_sums(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
+    """(num, den) of `bm3d_ref`, [n,h,w,3] each in the accumulator type: the weighted sum of the
+    estimates (two fraction bits) and the sum of the weights.  den >= 1 everywhere."""
+    from .infer import pad_index
+    a, _ = _images(img_u8, "bm3d_ref")
+    if np.dtype(dtype) not in (np.dtype(np.int64), np.dtype(np.uint32)):
+        raise ValueError(f"bm3d_ref: dtype must be np.int64 or np.uint32, got {dtype!r}")
+    sigma, s, K = check_bm3d(sigma, search, group, "bm3d_ref")
+    wt = np.int32 if np.dtype(dtype) == np.dtype(np.uint32) else np.int64   # everything but num / den
+    n, H, W = a.shape[:3]
+    rs = s // 2
+    R = rs + PATCH - 1
+    rows, cols = pad_index(np.arange(-R, H + R), H, "reflect"), pad_index(np.arange(-R, W + R), W, "reflect")
+    ri, rj = np.arange(1 - PATCH, H, STEP) + R, np.arange(1 - PATCH, W, STEP) + R   # reference corners in P
+    eh, ew = ri[-1] - ri[0] + PATCH, rj[-1] - rj[0] + PATCH                           # what their patches cover
+    H8, ar = hadamard(PATCH).astype(wt), np.arange(PATCH)
+    num, den = np.zeros((n, H, W, 3), dtype), np.zeros((n, H, W, 3), dtype)
+    for b in range(n):
+        P = a[b][rows][:, cols].astype(wt)
+        base = P[rs:rs + eh, rs:rs + ew]
+        keys = np.empty((s * s, len(ri), len(rj)), wt)
+        for idx in range(s * s):
+            dy, dx = idx // s - rs, idx % s - rs
+            e = ((base - P[rs + dy:rs + dy + eh, rs + dx:rs + dx + ew]) ** 2).sum(-1, dtype=wt)
+            v = sum(e[k:k + eh - PATCH + 1:STEP] for k in range(PATCH))
+            D = sum(v[:, k:k + ew - PATCH + 1:STEP] for k in range(PATCH))
+            ok = (D <= MATCH_BOUND) & bool(dy or dx)
+            keys[idx] = np.where(ok, (np.where(ok, D, 0) << 9) | idx, _NO_KEY)   # (D, idx) order in one integer
+        keys = np.sort(keys, axis=0)[:K - 1]
+        taken = (keys != _NO_KEY).sum(0)
+        ms = 1 << np.floor(np.log2(1 + taken)).astype(np.int64)   # (1 + taken <= 16: exact)
+        numP, denP = np.zeros(P.shape, dtype), np.zeros(P.shape, dtype)
+        for m in sorted(set(ms.ravel().tolist())):
+            ya, xb = np.nonzero(ms == m)
+            idx = np.concatenate([np.full((1, len(ya)), (s * s) // 2, wt), keys[:m - 1, ya, xb] & 511]).T   # [g,m]
+            Y = (ri[ya][:, None] + idx // s - rs)[:, :, None, None] + ar[:, None]
+            X = (rj[xb][:, None] + idx % s - rs)[:, :, None, None] + ar[None, :]
+            Y, X = np.broadcast_arrays(Y, X)
+            Hm, shift = hadamard(m).astype(wt), 4 + m.bit_length() - 1
+            C = _wht3(P[Y, X], Hm, H8)
+            assert np.abs(C).max() < 1 << 19
+            keep = np.abs(C) > bm3d_threshold(sigma, m)
+            keep[:, 0, 0, 0] = True
+            wgt = np.maximum(1, WEIGHT_SCALE // keep.sum((1, 2, 3), dtype=wt))[:, None, None, None]   # [g,1,1,1,3]
+            E = np.clip((_wht3(np.where(keep, C, 0), Hm, H8) + 8 * m) >> shift, 0, ESTIMATE_MAX)
+            np.add.at(numP, (Y, X), (wgt * E).astype(dtype))
+            np.add.at(denP, (Y, X), np.broadcast_to(wgt, E.shape).astype(dtype))
+        num[b], den[b] = numP[R:R + H, R:R + W], denP[R:R + H, R:R + W]   # members' pixels outside the image drop
+    assert den.min() >= 1 and den.max() < 1 << 22 and int(num.max()) < 1 << 32
+    return num, den
+
+
+def bm3d_ref(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
+    """Stage 1 of BM3D (block matching, hard thresholding of the group's 3-D transform, aggregation)
+    with the unnormalised Walsh-Hadamard transform, Sylvester order, in all three dimensions, as
+    exact integers: uint8 [n,h,w,3] or [h,w,3] -> the same shape and dtype.  BM3D with a Hadamard
+    transform is a known variant; it is NOT the Bior / DCT profile of Dabov et al.
+
+    sigma 1..40, search s odd in 3..21 (rs = s // 2), group K in {2, 4, 8, 16}; patches 8 x 8.
+    P: the image padded by rs + 7 with np.pad's "reflect" (dgan.infer.pad_index, any pad width).
+    Reference patches have their corners at (i, j) = (-7 + 3a, -7 + 3b), i <= h-1, j <= w-1, so
+    every pixel lies in one.  The candidates of a reference are the s*s patches at (i+dy, j+dx),
+    |dy|, |dx| <= rs, idx = (dy+rs) s + dx+rs, D = the sum over the patch and the three channels of
+    the squared difference (< 2^24; joint over RGB).  The group is the reference itself followed by
+    the first m-1 of the candidates with d != 0 and D <= 480000 in ascending (D, idx), where up to
+    K-1 are taken and m is the largest power of two <= 1 + the number taken.  Per channel the
+    m x 8 x 8 integers are transformed; a coefficient c stays iff |c| > T = isqrt(729 sigma^2 64 m
+    // 100) or it is the DC coefficient, N of them; the same transform again gives v = 64 m times the
+    estimate, E = clamp((v + 8m) >> (4 + log2 m), 0, 1020) (a floor shift; two fraction bits).
+    Every pixel of every member inside the image adds w E to num and w = max(1, 1024 // N) to den;
+    out = (num + 2 den) // (4 den).
+
+    Bounds: a patch position is taken by at most 7^2 = 49 references and a pixel lies in 64
+    positions: at most 3136 contributions, num <= 3136 * 1024 * 1020 < 2^32, den < 2^22,
+    coefficients < 2^19.  dtype np.uint32 runs num / den in uint32 and everything else in int32
+    and equals np.int64 (tests/test_bm3d.py); the bounds are asserted on every call."""
+    single = np.asarray(img_u8).ndim == 3
+    num, den = bm3d_sums(img_u8, sigma, search, group, dtype)
+    out = ((num + 2 * den) // (4 * den)).astype(np.uint8)
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
 # device code below: torch and the library are imported on use
 # ---------------------------------------------------------------------------
-MAX_PLANS = 8   # plans kept over both filters, least recently used first out (metrics._lru)
+MAX_PLANS = 8   # plans kept over all filters, least recently used first out (metrics._lru)
 _plans = {}     # (filter, n, h, w, device) -> the output buffers of the calls without `out`: one, and a
                 # second from the first call whose input is the first (a filter applied to its own result)
 _tables = {}    # (h, device) -> the device int16 weight table, uploaded once (at most MAX_H per device)
@@ -170,3 +308,20 @@ def nlm(x, h=10, template=7, search=21, out=None):
     if key not in _tables:
         _tables[key] = torch.from_numpy(nlm_table(h).astype(np.int16)).to(x.device)
     return ops.nlm(x, out, _tables[key], t, s)
+
+
+def bm3d(x, sigma=25, search=21, group=16, out=None):
+    """A dense uint8 NHWC device tensor [n,h,w,3] -> stage 1 of BM3D, equal to `bm3d_ref` bit for
+    bit.  `out` as in `median3`.  The uint32 accumulators (num and den, 24 bytes a pixel) are kept
+    with the output buffers; a repeated call allocates nothing, does no host sync and can be
+    captured in a graph."""
+    import torch
+    from . import ops
+    from .metrics import _lru
+    sigma, search, group = check_bm3d(sigma, search, group)
+    out = _device_pair(x, out, "bm3d")
+    if x.shape[0] == 0:
+        return out
+    ws = _lru(_plans, ("bm3d sums",) + tuple(x.shape[:3]) + (x.device,),
+              lambda: torch.empty(2 * x.numel(), dtype=torch.int32, device=x.device), MAX_PLANS)
+    return ops.bm3d(x, out, ws, sigma, search, group)

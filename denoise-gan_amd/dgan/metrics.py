@@ -188,15 +188,17 @@ def ssim(a, b, max_val=None, scale=1.0, shift=0.0, out=None):
 
 SCORES = ("psnr_noisy", "psnr_denoised", "ssim_noisy", "ssim_denoised")
 BASELINE_SCORES = ("psnr_baseline", "ssim_baseline")
-BASELINES = ("median3", "nlm")
+BASELINES = ("median3", "nlm", "bm3d")
+_BASELINE_KEYS = {"nlm": ("h", "template", "search"), "bm3d": ("sigma", "search", "group")}
 
 
 class Evaluator:
     """Scores a `Denoiser`'s frames against clean frames on the device: the noisy input and the
     denoised output stay where `Denoiser` holds them (uint8, dense), the clean frame is uploaded
     beside them, and only the 4 n scalars come back.  With a graph-capturing `Denoiser` the metrics
-    run eagerly on the same stream after the replay.  baseline "median3" or "nlm" (baseline_args:
-    the keywords of dgan.filters.nlm, h / template / search) also puts the noisy input through
+    run eagerly on the same stream after the replay.  baseline "median3", "nlm" or "bm3d"
+    (baseline_args: the keywords of dgan.filters.nlm, h / template / search, or of dgan.filters.bm3d,
+    sigma / search / group) also puts the noisy input through
     that classical filter on the device and scores it the same way: `psnr_baseline` and
     `ssim_baseline` join the result, 6 n scalars in all."""
 
@@ -207,13 +209,18 @@ class Evaluator:
         if baseline is not None and baseline not in BASELINES:
             raise ValueError(f"baseline must be None or one of {BASELINES}, got {baseline!r}")
         args = dict(baseline_args or {})
-        if args and baseline != "nlm":
-            raise ValueError(f"baseline_args apply to the baseline 'nlm' only, got {sorted(args)} with {baseline!r}")
-        if set(args) - {"h", "template", "search"}:
-            raise ValueError(f"baseline_args: unknown keys {sorted(set(args) - {'h', 'template', 'search'})}")
+        keys = _BASELINE_KEYS.get(baseline, ())
+        if args and not keys:
+            raise ValueError(f"baseline_args apply to the baselines {sorted(_BASELINE_KEYS)} only, got {sorted(args)} "
+                             f"with {baseline!r}")
+        if set(args) - set(keys):
+            raise ValueError(f"baseline_args: unknown keys {sorted(set(args) - set(keys))} for {baseline!r}")
         if baseline == "nlm":
-            args = dict(zip(("h", "template", "search"), filters.check_nlm(
+            args = dict(zip(keys, filters.check_nlm(
                 args.get("h", 10), args.get("template", 7), args.get("search", 21), "baseline_args")))
+        if baseline == "bm3d":
+            args = dict(zip(keys, filters.check_bm3d(
+                args.get("sigma", 25), args.get("search", 21), args.get("group", 16), "baseline_args")))
         self.denoiser, self.baseline, self.baseline_args = denoiser, baseline, args
         self.scores = SCORES + (BASELINE_SCORES if baseline else ())
         self._bufs = {}
@@ -234,7 +241,7 @@ class Evaluator:
         from . import filters
         if self.baseline == "median3":
             return filters.median3(f.u8_in)
-        return filters.nlm(f.u8_in, **self.baseline_args)
+        return getattr(filters, self.baseline)(f.u8_in, **self.baseline_args)
 
     def evaluate(self, noisy_u8, clean_u8):
         """uint8 [n,h,w,3] (or [h,w,3]) noisy and clean images -> {"psnr_noisy", "psnr_denoised",

@@ -1517,3 +1517,14 @@ def nlm(x, out, table, template, search):
         raise DGError(f"nlm table: expected a dense int16 vector on {x.device}")
     call("dg_nlm_u8", n, h, w, int(template), int(search), _p(table), table.numel(), _p(x), _p(out), _stream())
     return out
+
+
+def bm3d(x, out, ws, sigma, search, group):
+    """out[n,h,w,3] = stage 1 of BM3D (dg_bm3d_u8) of the dense uint8 images x[n,h,w,3]; out must
+    not be x.  ws: a dense int32 device vector of at least 2 * x.numel() elements (num and den)."""
+    n, h, w = _filter_pair(x, out, "bm3d")
+    if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.int32 or ws.dim() != 1 or not ws.is_contiguous()
+            or ws.device != x.device or ws.numel() < 2 * x.numel()):
+        raise DGError(f"bm3d workspace: expected a dense int32 vector of {2 * x.numel()} elements on {x.device}")
+    call("dg_bm3d_u8", n, h, w, int(sigma), int(search), int(group), _p(x), _p(ws), ws.numel() * 4, _p(out), _stream())
+    return out

@@ -16,8 +16,9 @@ the two directories are compared directly: psnr, ssim.  With --jpeg_quality Q in
 quality Q with 4:2:0 subsampling on the device (dgan.jpeg, the degradation the training pipeline
 applies, bit for bit what Pillow's codec returns), and the scores are the same.  The metrics are
 the tf.image.psnr / tf.image.ssim defaults on uint8 RGB (max_val 255), accumulated in fp64.
---baseline median3 | nlm also puts every noisy image through that classical filter on the device
-(dgan.filters; --nlm_h / --nlm_template / --nlm_search) and scores the result the same way:
+--baseline median3 | nlm | bm3d also puts every noisy image through that classical filter on the
+device (dgan.filters; --nlm_h / --nlm_template / --nlm_search, --bm3d_sigma / --bm3d_search /
+--bm3d_group) and scores the result the same way:
 psnr_baseline, ssim_baseline, with and without --model.
 """
 import json
@@ -41,11 +42,14 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
-parser.add_argument("--baseline", default=None, choices=["median3", "nlm"],
-                    help="Also score a classical filter of the noisy image: the 3x3 median or non-local means.")
+parser.add_argument("--baseline", default=None, choices=["median3", "nlm", "bm3d"],
+                    help="Also score a classical filter of the noisy image: the 3x3 median, non-local means or BM3D.")
 parser.add_argument("--nlm_h", default=10, type=int, help="Non-local means: the filter strength (1..40).")
 parser.add_argument("--nlm_template", default=7, type=int, help="Non-local means: the patch size (3, 5 or 7).")
 parser.add_argument("--nlm_search", default=21, type=int, help="Non-local means: the search window (odd, 3..21).")
+parser.add_argument("--bm3d_sigma", default=25, type=int, help="BM3D: the noise level it is set for (1..40).")
+parser.add_argument("--bm3d_search", default=21, type=int, help="BM3D: the search window (odd, 3..21).")
+parser.add_argument("--bm3d_group", default=16, type=int, help="BM3D: the most patches of a group (2, 4, 8 or 16).")
 parser.add_argument("--json", default=None, type=str, help="Also write the scores and their means to this file.")
 
 
@@ -76,15 +80,23 @@ def _read_rgb(path):
 
 
 def baseline_args(args):
-    """The keywords of dgan.filters.nlm that --baseline nlm asks for ({} for the other baselines).
-    ValueError naming a bad --nlm_* value, or one given without --baseline nlm."""
-    from dgan.filters import check_nlm
+    """The keywords of dgan.filters.nlm / bm3d that --baseline nlm / bm3d asks for ({} for the other
+    baselines).  ValueError naming a bad --nlm_* / --bm3d_* value, or one given without its baseline.
+    A namespace without the --bm3d_* attributes has their defaults."""
+    from dgan.filters import check_bm3d, check_nlm
     given = (args.nlm_h, args.nlm_template, args.nlm_search)
-    if args.baseline != "nlm":
-        if given != (10, 7, 21):
-            raise ValueError("--nlm_h / --nlm_template / --nlm_search need --baseline nlm")
-        return {}
-    return dict(zip(("h", "template", "search"), check_nlm(*given, what="--baseline nlm")))
+    bm3d = tuple(d if v is None else v for v, d in ((getattr(args, "bm3d_sigma", None), 25),
+                                                    (getattr(args, "bm3d_search", None), 21),
+                                                    (getattr(args, "bm3d_group", None), 16)))
+    if args.baseline != "nlm" and given != (10, 7, 21):
+        raise ValueError("--nlm_h / --nlm_template / --nlm_search need --baseline nlm")
+    if args.baseline != "bm3d" and bm3d != (25, 21, 16):
+        raise ValueError("--bm3d_sigma / --bm3d_search / --bm3d_group need --baseline bm3d")
+    if args.baseline == "nlm":
+        return dict(zip(("h", "template", "search"), check_nlm(*given, what="--baseline nlm")))
+    if args.baseline == "bm3d":
+        return dict(zip(("sigma", "search", "group"), check_bm3d(*bm3d, what="--baseline bm3d")))
+    return {}
 
 
 def summarize(rows):
@@ -143,7 +155,7 @@ def main(argv=None):
             a = torch.from_numpy(noisy[None]).cuda() if image_dir is not None else jpeg_roundtrip(b, args.jpeg_quality)
             row = {"psnr": float(metrics.psnr(a, b).item()), "ssim": float(metrics.ssim(a, b).item())}
             if args.baseline:
-                c = filters.median3(a) if args.baseline == "median3" else filters.nlm(a, **nlm_args)
+                c = getattr(filters, args.baseline)(a, **nlm_args)
                 row.update(psnr_baseline=float(metrics.psnr(c, b).item()), ssim_baseline=float(metrics.ssim(c, b).item()))
         rows.append({"name": image_name, **row})
         print(image_name + "".join(f" {k} {v:.4f}" for k, v in row.items()))

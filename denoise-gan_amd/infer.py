@@ -8,7 +8,8 @@ that names the width.  Images are read and written with Pillow, as RGB; each kee
 file name.  Whole images are padded to a multiple of 256 by default; --tile T (a multiple of 256)
 with --margin M runs T x T tiles with M pixels of context instead, --batch of them per forward.
 --post median3 puts the denoised frame through a 3x3 median on the device before it is read back
-(dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95).  --format jpg writes
+(dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95); --post bm3d through
+BM3D set for --bm3d_sigma (dgan.filters.bm3d).  --format jpg writes
 <stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
 only the file's bytes are read back; --format png writes <stem>.png the same way, lossless
 (dgan.png.png_encode).  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
@@ -33,8 +34,9 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
-parser.add_argument("--post", default=None, choices=["median3"],
+parser.add_argument("--post", default=None, choices=["median3", "bm3d"],
                     help="A classical filter applied to the denoised image on the device (default: none).")
+parser.add_argument("--bm3d_sigma", default=25, type=int, help="The noise level --post bm3d is set for (1..40).")
 parser.add_argument("--format", default="keep", choices=["keep", "jpg", "png"],
                     help="keep: Pillow writes every image under its own name; jpg / png: baseline JPEG or PNG files "
                          "encoded on the device.")
@@ -100,12 +102,25 @@ def resized(frame, size, filter):
     return resize_pil(frame.contiguous(), size[1], size[0], filter)
 
 
+def post_filtered(frame, args):
+    """The device frame through --post (dgan.filters), or itself."""
+    if args.post == "median3":
+        from dgan.filters import median3
+        return median3(frame)
+    if args.post == "bm3d":
+        from dgan.filters import bm3d
+        return bm3d(frame.contiguous(), args.bm3d_sigma)
+    return frame
+
+
 def main(argv=None):
     from PIL import Image
     from dgan.infer import Denoiser
     args = parser.parse_args(argv)
     if not 1 <= args.jpeg_quality <= 100:
         parser.error(f"--jpeg_quality must be in 1..100, got {args.jpeg_quality}")
+    if not 1 <= args.bm3d_sigma <= 40:
+        parser.error(f"--bm3d_sigma must be in 1..40, got {args.bm3d_sigma}")
     size = parse_size(args.resize)
     image_dir = os.path.expanduser(os.path.expandvars(args.image_dir))
     output_dir = os.path.expanduser(os.path.expandvars(args.output_dir))
@@ -117,10 +132,7 @@ def main(argv=None):
     for image_path in image_paths:
         noisy = read_image(image_path, args.decode)
         if args.format != "keep":
-            frame = denoiser.run(noisy).u8_out
-            if args.post == "median3":
-                from dgan.filters import median3
-                frame = median3(frame)
+            frame = post_filtered(denoiser.run(noisy).u8_out, args)
             frame = resized(frame, size, args.resize_filter)
             out_path = os.path.join(output_dir, os.path.splitext(os.path.basename(image_path))[0] + "." + args.format)
             if args.format == "jpg":
@@ -133,10 +145,7 @@ def main(argv=None):
                 f.write(data)
             print(f"{image_path} -> {out_path} {frame.shape[2]}x{frame.shape[1]}")
             continue
-        frame = denoiser.run(noisy).u8_out
-        if args.post == "median3":
-            from dgan.filters import median3
-            frame = median3(frame)
+        frame = post_filtered(denoiser.run(noisy).u8_out, args)
         clean = resized(frame, size, args.resize_filter).cpu().numpy()[0]
         out_path = os.path.join(output_dir, os.path.basename(image_path))
         Image.fromarray(clean, "RGB").save(out_path)

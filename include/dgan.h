@@ -808,6 +808,18 @@ int dg_median3_u8(int n, int h, int w, const unsigned char *in, unsigned char *o
 int dg_nlm_u8(int n, int h, int w, int t, int s, const unsigned short *table, int table_len, const unsigned char *in,
               unsigned char *out, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * BM3D, stage 1 (dgan/filters.py bm3d_ref: block matching over a search x search window, hard
+ * thresholding of each group's 3-D Walsh-Hadamard transform, aggregation).  Dense RGB images
+ * [n][h][w][3] -> the same shape, any byte alignment; integers only, equal to the numpy reference
+ * bit for bit, and two calls give the same bits (the aggregation's uint32 atomic adds commute).
+ * sigma 1..40, search odd in 3..21, group 2, 4, 8 or 16; `out` must not be `in`.
+ * ws: dg_bm3d_ws_bytes(n, h, w) bytes of device memory, 4-byte aligned: the uint32 planes num and
+ * den, [n][h][w][3] each, which the call clears itself (three launches: clear, filter, divide). */
+int dg_bm3d_ws_bytes(int n, int h, int w, size_t *ws_bytes);
+int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in, void *ws,
+               size_t ws_bytes, unsigned char *out, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
