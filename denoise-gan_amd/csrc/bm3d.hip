@@ -42,85 +42,9 @@
 //
 // LDS at search 21: pixels 49 x 49, N 42 x 42, V 2 x 8 x 29, best 64 x 16, counts 64, and the shared
 // buffer (keys 64 x 147 | row sums 49 x 42 | accumulators 42 x 42 x 6) 10584 dwords: 65204 bytes.
-#include "common.h"
+#include "bm3d_common.h"
 
 namespace dg {
-
-constexpr int BT = 256;                       // threads of a workgroup
-constexpr int BR = 8;                         // reference patches per tile side
-constexpr int BP = 8, BSTEP = 3;              // patch side, reference step
-constexpr int BEXT = BSTEP * (BR - 1) + BP;   // pixels a tile's reference patches cover: 29
-constexpr int BRS = 10;                       // largest search radius
-constexpr int BROWS = 7;                      // rows of offsets per selection
-constexpr int BBEST = 16;                     // dwords per reference's best list (15 used)
-constexpr unsigned BNONE = 0xffffffffu;       // the key of a candidate that does not match
-constexpr unsigned BMATCH = 480000u;
-constexpr int BLDS_MAX = 64 * 1024;
-static_assert(BR * BEXT <= BT && BR * BR <= BT, "phase 1 / phase 2: one thread per role");
-
-struct Bm3dGeom {
-    int h, w, nry, nrx;   // image, reference grid
-    int s, rs, K;         // search, its radius, group size
-    int se, ne;           // staged extent 29 + 2 rs, extent of N 22 + 2 rs
-    int ae, a0;           // accumulator extent in LDS and its first staged row / column
-    int shared;           // dwords of the shared buffer
-    int T[5];             // thresholds of m = 1, 2, 4, 8, 16
-};
-
-// np.pad's "reflect" for any pad width (dgan/infer.py pad_index)
-__device__ __forceinline__ int breflect(int v, int size) {
-    if (size == 1) return 0;
-    const int p = 2 * (size - 1);
-    int j = v % p;
-    if (j < 0) j += p;
-    return j >= size ? p - j : j;
-}
-
-// the value of lane ^ MASK
-template <int MASK>
-__device__ __forceinline__ int lane_xor(int v) {
-    if constexpr (MASK == 1) return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);        // quad_perm [1,0,3,2]
-    else if constexpr (MASK == 2) return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
-    else if constexpr (MASK < 32) return __builtin_amdgcn_ds_swizzle(v, (MASK << 10) | 0x1f);  // and 31, or 0, xor MASK
-    else return __shfl_xor(v, 32);
-}
-
-template <int MASK>
-__device__ __forceinline__ int lane_butterfly(int v, int lane) {
-    const int o = lane_xor<MASK>(v);
-    return (lane & MASK) ? o - v : v + o;
-}
-
-// H8 (x) H8 over the 64 lanes (lane = 8 row + column), unnormalised
-__device__ __forceinline__ int patch_wht(int v, int lane) {
-    v = lane_butterfly<1>(v, lane);
-    v = lane_butterfly<2>(v, lane);
-    v = lane_butterfly<4>(v, lane);
-    v = lane_butterfly<8>(v, lane);
-    v = lane_butterfly<16>(v, lane);
-    return lane_butterfly<32>(v, lane);
-}
-
-// H_M along the group, Sylvester order, in registers
-template <int M>
-__device__ __forceinline__ void group_wht(int (&x)[M]) {
-#pragma unroll
-    for (int len = 1; len < M; len <<= 1)
-#pragma unroll
-        for (int i = 0; i < M; i += 2 * len)
-#pragma unroll
-            for (int j = i; j < i + len; ++j) {
-                const int a = x[j], b = x[j + len];
-                x[j] = a + b;
-                x[j + len] = a - b;
-            }
-}
-
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-    return v;
-}
 
 // One group: reference (ry, rx) of the tile with the M - 1 first entries of its best list.
 template <int M>
@@ -361,10 +285,10 @@ int dg_bm3d_ws_bytes(int n, int h, int w, size_t *ws_bytes) {
     return DG_OK;
 }
 
-int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in, void *ws,
-               size_t ws_bytes, unsigned char *out, dg_stream_t stream) {
-    using namespace dg;
-    const char *name = "bm3d_u8";
+namespace dg {
+
+int bm3d_prepare(const char *name, int n, int h, int w, int sigma, int search, int group, const void *in, const void *ws,
+                 size_t ws_bytes, const void *out, Bm3dGeom *geom, size_t *lds_bytes) {
     size_t need = 0;
     if (int rc = dg_bm3d_ws_bytes(n, h, w, &need)) return rc;
     DG_ARG(sigma >= 1 && sigma <= 40, "%s: sigma must be in 1..40, got %d", name, sigma);
@@ -376,7 +300,7 @@ int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsi
     DG_ARG(in && out && ws, "%s: NULL tensor", name);
     DG_ARG(in != out, "%s: the output must not be the input", name);
     DG_ARG(ws_bytes >= need, "%s: the workspace holds %zu bytes, %zu needed", name, ws_bytes, need);
-    Bm3dGeom g;
+    Bm3dGeom &g = *geom;
     g.h = h;
     g.w = w;
     g.nry = (h + BP - 2) / BSTEP + 1;   // corners -7 + 3 a <= h - 1
@@ -395,15 +319,38 @@ int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsi
     if (g.shared < g.se * g.ne) g.shared = g.se * g.ne;
     if (g.shared < g.ae * g.ae * 6) g.shared = g.ae * g.ae * 6;
     for (int l = 0; l < 5; ++l) g.T[l] = isqrt_int(729L * sigma * sigma * BP * BP * (1 << l) / 100);
-    const size_t lds = (size_t)(fixed + g.shared) * sizeof(int);
-    DG_ARG(lds <= (size_t)BLDS_MAX, "%s: %zu bytes of LDS", name, lds);
+    *lds_bytes = (size_t)(fixed + g.shared) * sizeof(int);
+    DG_ARG(*lds_bytes <= (size_t)BLDS_MAX, "%s: %zu bytes of LDS", name, *lds_bytes);
+    return DG_OK;
+}
+
+static unsigned sweep_blocks(long count) { return (unsigned)((count + 255) / 256 < 65536 ? (count + 255) / 256 : 65536); }
+
+void bm3d_clear(long count, unsigned *sums, dg_stream_t stream) {
+    hipLaunchKernelGGL(k_bm3d_clear, dim3(sweep_blocks(count)), dim3(256), 0, (hipStream_t)stream, count, sums);
+}
+
+void bm3d_divide(long count, const unsigned *num, const unsigned *den, unsigned char *out, dg_stream_t stream) {
+    hipLaunchKernelGGL(k_bm3d_divide, dim3(sweep_blocks(2 * count)), dim3(256), 0, (hipStream_t)stream, count, num, den,
+                       out);
+}
+
+}  // namespace dg
+
+int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in, void *ws,
+               size_t ws_bytes, unsigned char *out, dg_stream_t stream) {
+    using namespace dg;
+    const char *name = "bm3d_u8";
+    Bm3dGeom g;
+    size_t lds = 0;
+    if (int rc = bm3d_prepare(name, n, h, w, sigma, search, group, in, ws, ws_bytes, out, &g, &lds)) return rc;
+    if (n == 0) return DG_OK;
     const long count = (long)n * h * w * 3;
     unsigned *num = static_cast<unsigned *>(ws), *den = num + count;
-    const unsigned blocks = (unsigned)((2 * count + 255) / 256 < 65536 ? (2 * count + 255) / 256 : 65536);
-    hipLaunchKernelGGL(k_bm3d_clear, dim3(blocks), dim3(256), 0, (hipStream_t)stream, 2 * count, num);
+    bm3d_clear(2 * count, num, stream);
     hipLaunchKernelGGL(k_bm3d, dim3(dg_cdiv(g.nrx, BR), dg_cdiv(g.nry, BR), n), dim3(BT), lds, (hipStream_t)stream, g, in,
                        num, den);
-    hipLaunchKernelGGL(k_bm3d_divide, dim3(blocks), dim3(256), 0, (hipStream_t)stream, count, num, den, out);
+    bm3d_divide(count, num, den, out, stream);
     DG_LAUNCHED(name);
     return DG_OK;
 }

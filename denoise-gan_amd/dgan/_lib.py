@@ -181,6 +181,7 @@ _SIGS = {
     "dg_nlm_u8": (c_int, [c_int] * 5 + [_P, c_int, _P, _P, _P]),
     "dg_bm3d_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
     "dg_bm3d_u8": (c_int, [c_int] * 6 + [_P, _P, c_size_t, _P, _P]),
+    "dg_bm3d_wiener_u8": (c_int, [c_int] * 6 + [_P, _P, _P, c_size_t, _P, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -21,6 +21,9 @@ post-filter (infer.py --post median3).
     bm3d       stage 1 (hard thresholding) of BM3D with the unnormalised Walsh-Hadamard transform in
                all three dimensions: `bm3d_ref` states it in full.
 
+    bm3d_wiener  stage 2 (the collaborative Wiener filter) on a pilot estimate: `bm3d_wiener_ref`.
+    bm3d2      both stages, stage 1's output as the pilot: `bm3d2_ref`.
+
 `nlm` is the non-local means of Buades et al. with one weight for the three channels.  It is NOT
 claimed equal to cv2.fastNlMeansDenoisingColored, which filters in Lab with separate luminance and
 colour strengths and its own fixed-point weights.
@@ -28,7 +31,7 @@ colour strengths and its own fixed-point weights.
 `bm3d` is BM3D (Dabov et al.) with a Hadamard transform, a known cheap variant.  It is NOT the
 Bior / DCT profile of the original paper and is not claimed equal to any other implementation.
 
-`median3_ref` / `nlm_table` / `nlm_ref` / `bm3d_ref` are pure numpy and import neither torch nor the library.
+`median3_ref` / `nlm_table` / `nlm_ref` / `bm3d_ref` / `bm3d_wiener_ref` / `bm3d2_ref` are pure numpy and import neither torch nor the library.
 """
 import math
 
@@ -161,44 +164,59 @@ def _wht3(G, Hm, H8):
     return np.einsum("ab,gkibc->gkiac", H8, G)
 
 
+def _bm3d_groups(P, H, W, s, K, bound, wt):
+    """The groups of one padded image P [H+2R, W+2R, 3] (R = s // 2 + 7, type wt), matched on P at
+    D <= bound: (m, Y, X) per group size m, Y and X [g,m,8,8] the members' pixels in P."""
+    rs = s // 2
+    R = rs + PATCH - 1
+    ri, rj = np.arange(1 - PATCH, H, STEP) + R, np.arange(1 - PATCH, W, STEP) + R   # reference corners in P
+    eh, ew = ri[-1] - ri[0] + PATCH, rj[-1] - rj[0] + PATCH                           # what their patches cover
+    ar = np.arange(PATCH)
+    base = P[rs:rs + eh, rs:rs + ew]
+    keys = np.empty((s * s, len(ri), len(rj)), wt)
+    for idx in range(s * s):
+        dy, dx = idx // s - rs, idx % s - rs
+        e = ((base - P[rs + dy:rs + dy + eh, rs + dx:rs + dx + ew]) ** 2).sum(-1, dtype=wt)
+        v = sum(e[k:k + eh - PATCH + 1:STEP] for k in range(PATCH))
+        D = sum(v[:, k:k + ew - PATCH + 1:STEP] for k in range(PATCH))
+        ok = (D <= bound) & bool(dy or dx)
+        keys[idx] = np.where(ok, (np.where(ok, D, 0) << 9) | idx, _NO_KEY)   # (D, idx) order in one integer
+    keys = np.sort(keys, axis=0)[:K - 1]
+    taken = (keys != _NO_KEY).sum(0)
+    ms = 1 << np.floor(np.log2(1 + taken)).astype(np.int64)   # (1 + taken <= 16: exact)
+    for m in sorted(set(ms.ravel().tolist())):
+        ya, xb = np.nonzero(ms == m)
+        idx = np.concatenate([np.full((1, len(ya)), (s * s) // 2, wt), keys[:m - 1, ya, xb] & 511]).T   # [g,m]
+        Y = (ri[ya][:, None] + idx // s - rs)[:, :, None, None] + ar[:, None]
+        X = (rj[xb][:, None] + idx % s - rs)[:, :, None, None] + ar[None, :]
+        yield (m,) + tuple(np.broadcast_arrays(Y, X))
+
+
+def _bm3d_setup(a, sigma, search, group, dtype, what):
+    """The checked parameters, the working type, the pad R and the padded rows / columns."""
+    from .infer import pad_index
+    if np.dtype(dtype) not in (np.dtype(np.int64), np.dtype(np.uint32)):
+        raise ValueError(f"{what}: dtype must be np.int64 or np.uint32, got {dtype!r}")
+    sigma, s, K = check_bm3d(sigma, search, group, what)
+    wt = np.int32 if np.dtype(dtype) == np.dtype(np.uint32) else np.int64   # everything but num / den
+    H, W = a.shape[1:3]
+    R = s // 2 + PATCH - 1
+    rows, cols = pad_index(np.arange(-R, H + R), H, "reflect"), pad_index(np.arange(-R, W + R), W, "reflect")
+    return sigma, s, K, wt, R, rows, cols
+
+
 def bm3d_sums(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
     """(num, den) of `bm3d_ref`, [n,h,w,3] each in the accumulator type: the weighted sum of the
     estimates (two fraction bits) and the sum of the weights.  den >= 1 everywhere."""
-    from .infer import pad_index
     a, _ = _images(img_u8, "bm3d_ref")
-    if np.dtype(dtype) not in (np.dtype(np.int64), np.dtype(np.uint32)):
-        raise ValueError(f"bm3d_ref: dtype must be np.int64 or np.uint32, got {dtype!r}")
-    sigma, s, K = check_bm3d(sigma, search, group, "bm3d_ref")
-    wt = np.int32 if np.dtype(dtype) == np.dtype(np.uint32) else np.int64   # everything but num / den
+    sigma, s, K, wt, R, rows, cols = _bm3d_setup(a, sigma, search, group, dtype, "bm3d_ref")
     n, H, W = a.shape[:3]
-    rs = s // 2
-    R = rs + PATCH - 1
-    rows, cols = pad_index(np.arange(-R, H + R), H, "reflect"), pad_index(np.arange(-R, W + R), W, "reflect")
-    ri, rj = np.arange(1 - PATCH, H, STEP) + R, np.arange(1 - PATCH, W, STEP) + R   # reference corners in P
-    eh, ew = ri[-1] - ri[0] + PATCH, rj[-1] - rj[0] + PATCH                           # what their patches cover
-    H8, ar = hadamard(PATCH).astype(wt), np.arange(PATCH)
+    H8 = hadamard(PATCH).astype(wt)
     num, den = np.zeros((n, H, W, 3), dtype), np.zeros((n, H, W, 3), dtype)
     for b in range(n):
         P = a[b][rows][:, cols].astype(wt)
-        base = P[rs:rs + eh, rs:rs + ew]
-        keys = np.empty((s * s, len(ri), len(rj)), wt)
-        for idx in range(s * s):
-            dy, dx = idx // s - rs, idx % s - rs
-            e = ((base - P[rs + dy:rs + dy + eh, rs + dx:rs + dx + ew]) ** 2).sum(-1, dtype=wt)
-            v = sum(e[k:k + eh - PATCH + 1:STEP] for k in range(PATCH))
-            D = sum(v[:, k:k + ew - PATCH + 1:STEP] for k in range(PATCH))
-            ok = (D <= MATCH_BOUND) & bool(dy or dx)
-            keys[idx] = np.where(ok, (np.where(ok, D, 0) << 9) | idx, _NO_KEY)   # (D, idx) order in one integer
-        keys = np.sort(keys, axis=0)[:K - 1]
-        taken = (keys != _NO_KEY).sum(0)
-        ms = 1 << np.floor(np.log2(1 + taken)).astype(np.int64)   # (1 + taken <= 16: exact)
         numP, denP = np.zeros(P.shape, dtype), np.zeros(P.shape, dtype)
-        for m in sorted(set(ms.ravel().tolist())):
-            ya, xb = np.nonzero(ms == m)
-            idx = np.concatenate([np.full((1, len(ya)), (s * s) // 2, wt), keys[:m - 1, ya, xb] & 511]).T   # [g,m]
-            Y = (ri[ya][:, None] + idx // s - rs)[:, :, None, None] + ar[:, None]
-            X = (rj[xb][:, None] + idx % s - rs)[:, :, None, None] + ar[None, :]
-            Y, X = np.broadcast_arrays(Y, X)
+        for m, Y, X in _bm3d_groups(P, H, W, s, K, MATCH_BOUND, wt):
             Hm, shift = hadamard(m).astype(wt), 4 + m.bit_length() - 1
             C = _wht3(P[Y, X], Hm, H8)
             assert np.abs(C).max() < 1 << 19
@@ -241,6 +259,95 @@ def bm3d_ref(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
     num, den = bm3d_sums(img_u8, sigma, search, group, dtype)
     out = ((num + 2 * den) // (4 * den)).astype(np.uint8)
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
+# BM3D, stage 2
+# ---------------------------------------------------------------------------
+MATCH_BOUND2 = 76800      # a candidate matches when the pilot's D <= 400 per sample * 192 samples
+ENERGY_MAX = 1 << 23      # the pilot's energy is clamped here: Wq is 256 from here on for sigma <= 40
+WIENER_ONE = 256          # the Wiener weight Wq carries eight fraction bits
+
+
+def bm3d_wiener_sums(noisy_u8, pilot_u8, sigma=25, search=21, group=16, dtype=np.int64):
+    """(num, den) of `bm3d_wiener_ref`, as `bm3d_sums` returns them."""
+    what = "bm3d_wiener_ref"
+    a, _ = _images(noisy_u8, what)
+    p, _ = _images(pilot_u8, what)
+    if np.shape(noisy_u8) != np.shape(pilot_u8):
+        raise ValueError(f"{what}: the pilot {np.shape(pilot_u8)} does not match the noisy images {np.shape(noisy_u8)}")
+    sigma, s, K, wt, R, rows, cols = _bm3d_setup(a, sigma, search, group, dtype, what)
+    n, H, W = a.shape[:3]
+    H8 = hadamard(PATCH).astype(wt)
+    num, den = np.zeros((n, H, W, 3), dtype), np.zeros((n, H, W, 3), dtype)
+    for b in range(n):
+        Pz, Py = a[b][rows][:, cols].astype(wt), p[b][rows][:, cols].astype(wt)
+        numP, denP = np.zeros(Pz.shape, dtype), np.zeros(Pz.shape, dtype)
+        for m, Y, X in _bm3d_groups(Py, H, W, s, K, MATCH_BOUND2, wt):
+            Hm, lg = hadamard(m).astype(wt), m.bit_length() - 1
+            Cy, Cz = _wht3(Py[Y, X], Hm, H8), _wht3(Pz[Y, X], Hm, H8)
+            assert max(np.abs(Cy).max(), np.abs(Cz).max()) < 1 << 18
+            e = Cy.astype(np.int64) ** 2 >> (6 + lg)            # the one 64-bit product: < 2^36, e < 2^26
+            assert e.max() < 1 << 26
+            e = np.minimum(e, ENERGY_MAX).astype(np.uint32)
+            d = e + np.uint32(sigma * sigma)
+            Wq = ((WIENER_ONE * e + d // 2) // d).astype(wt)    # 256 e + d // 2 < 2^32
+            Wq[:, 0, 0, 0] = WIENER_ONE
+            assert Wq.min() >= 0 and Wq.max() <= WIENER_ONE
+            F = (Wq * Cz + WIENER_ONE // 2) >> 8
+            assert (np.abs(F) <= np.abs(Cz)).all()
+            v = _wht3(F, Hm, H8)
+            assert np.abs(v).max() <= 1 << 28
+            E = np.clip((v + 8 * m) >> (4 + lg), 0, ESTIMATE_MAX)
+            N2 = np.maximum(1, ((Wq * Wq).sum((1, 2, 3), dtype=wt) + (1 << 15)) >> 16)
+            assert N2.max() <= 1024
+            wgt = np.maximum(1, WEIGHT_SCALE // N2)[:, None, None, None]   # [g,1,1,1,3]
+            np.add.at(numP, (Y, X), (wgt * E).astype(dtype))
+            np.add.at(denP, (Y, X), np.broadcast_to(wgt, E.shape).astype(dtype))
+        num[b], den[b] = numP[R:R + H, R:R + W], denP[R:R + H, R:R + W]
+    assert den.min() >= 1 and den.max() < 1 << 22 and int(num.max()) < 1 << 32
+    return num, den
+
+
+def bm3d_group_sizes(pilot_u8, search=21, group=16):
+    """{m: the number of groups of that size} that stage 2's matching forms on one pilot [h,w,3]."""
+    a, single = _images(pilot_u8, "bm3d_group_sizes")
+    if not single:
+        raise ValueError(f"bm3d_group_sizes: expected one image [h,w,3], got {a.shape}")
+    _, s, K, wt, _, rows, cols = _bm3d_setup(a, 1, search, group, np.int64, "bm3d_group_sizes")
+    return {m: len(Y) for m, Y, _ in _bm3d_groups(a[0][rows][:, cols].astype(wt), *a.shape[1:3], s, K, MATCH_BOUND2, wt)}
+
+
+def bm3d_wiener_ref(noisy_u8, pilot_u8, sigma=25, search=21, group=16, dtype=np.int64):
+    """Stage 2 of BM3D (block matching on a pilot estimate, a Wiener weight per coefficient of the
+    group's 3-D transform, aggregation) as exact integers: uint8 [n,h,w,3] or [h,w,3] twice, of the
+    same shape -> that shape and dtype.  Everything not said here is `bm3d_ref`'s.
+
+    D is the squared difference of PILOT patches, and a candidate matches iff D <= 76800; both
+    images are padded with the same indices and the group's positions serve both.  Per channel,
+    Cy = the transform of the pilot's m x 8 x 8 integers, Cz of the noisy ones (|C| <= 255 * 64 m <
+    2^18).  With lg = log2 m: e = min((Cy Cy) >> (6 + lg), 2^23), the pilot's energy on the
+    normalised scale (the product < 2^36; e < 2^26 before the clamp); d = e + sigma^2;
+    Wq = (256 e + d // 2) // d in 0..256 (256 e + d // 2 < 2^32; every e >= 2^23 gives 256 for
+    sigma <= 40, so the clamp loses nothing), and Wq = 256 for the DC coefficient, which returns a
+    flat frame unchanged.  F = (Wq Cz + 128) >> 8 (a floor shift, |F| <= |Cz|); v = the transform of
+    F (|v| <= 2^28); E = clamp((v + 8m) >> (4 + lg), 0, 1020).  The group's weight per channel:
+    N2 = max(1, (sum Wq^2 + 2^15) >> 16) in 1..1024, w = max(1, 1024 // N2).  num, den and the output
+    as in `bm3d_ref`, with its bounds.
+
+    dtype np.uint32 runs num / den in uint32, the Cy Cy product in 64 bits, the division in uint32
+    and everything else in int32, and equals np.int64 (tests/test_bm3d2.py); the bounds are
+    asserted on every call."""
+    single = np.asarray(noisy_u8).ndim == 3
+    num, den = bm3d_wiener_sums(noisy_u8, pilot_u8, sigma, search, group, dtype)
+    out = ((num + 2 * den) // (4 * den)).astype(np.uint8)
+    return out[0] if single else out
+
+
+def bm3d2_ref(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
+    """Both stages of BM3D with one set of parameters: `bm3d_wiener_ref` with `bm3d_ref`'s output as
+    the pilot."""
+    return bm3d_wiener_ref(img_u8, bm3d_ref(img_u8, sigma, search, group, dtype), sigma, search, group, dtype)
 
 
 # ---------------------------------------------------------------------------
@@ -325,3 +432,47 @@ def bm3d(x, sigma=25, search=21, group=16, out=None):
     ws = _lru(_plans, ("bm3d sums",) + tuple(x.shape[:3]) + (x.device,),
               lambda: torch.empty(2 * x.numel(), dtype=torch.int32, device=x.device), MAX_PLANS)
     return ops.bm3d(x, out, ws, sigma, search, group)
+
+
+def bm3d_wiener(x, pilot, sigma=25, search=21, group=16, out=None):
+    """Dense uint8 NHWC device tensors [n,h,w,3], the noisy frame and a pilot estimate of the clean
+    one (stage 1's output, or any other: a network's) -> stage 2 of BM3D, equal to
+    `bm3d_wiener_ref` bit for bit.  `out` as in `median3`, and never the pilot either (the plan keeps
+    a third buffer for the call whose two inputs are its first two).  The accumulators are the ones
+    `bm3d` keeps; a repeated call allocates nothing, does no host sync and can be captured."""
+    import torch
+    from . import ops
+    from .metrics import _lru
+    sigma, search, group = check_bm3d(sigma, search, group, "bm3d_wiener")
+    if not isinstance(pilot, torch.Tensor) or pilot.dtype != torch.uint8 or not isinstance(x, torch.Tensor) \
+            or pilot.shape != x.shape or pilot.device != x.device or not pilot.is_contiguous():
+        raise ValueError(f"bm3d_wiener: the pilot must be a dense uint8 tensor like the input, got "
+                         f"{getattr(pilot, 'dtype', type(pilot))} {tuple(getattr(pilot, 'shape', ()))}")
+    if out is pilot:
+        raise ValueError("bm3d_wiener: out must not be the pilot")
+    given = out is not None
+    out = _device_pair(x, out, "bm3d_wiener")
+    if x.shape[0] == 0:
+        return out
+    if not given and out.data_ptr() == pilot.data_ptr():
+        bufs = _plans[("bm3d_wiener",) + tuple(x.shape[:3]) + (x.device,)]
+        while len(bufs) < 3:
+            bufs.append(torch.empty_like(x))
+        out = next(b for b in bufs if b.data_ptr() not in (x.data_ptr(), pilot.data_ptr()))
+    ws = _lru(_plans, ("bm3d sums",) + tuple(x.shape[:3]) + (x.device,),
+              lambda: torch.empty(2 * x.numel(), dtype=torch.int32, device=x.device), MAX_PLANS)
+    return ops.bm3d_wiener(x, pilot, out, ws, sigma, search, group)
+
+
+def bm3d2(x, sigma=25, search=21, group=16, out=None):
+    """A dense uint8 NHWC device tensor [n,h,w,3] -> both stages of BM3D, equal to `bm3d2_ref` bit
+    for bit: `bm3d` into a pilot buffer kept with the plans, then `bm3d_wiener`.  `out` as in
+    `median3`; a repeated call allocates nothing, does no host sync and can be captured."""
+    import torch
+    from .metrics import _lru
+    sigma, search, group = check_bm3d(sigma, search, group, "bm3d2")
+    out = _device_pair(x, out, "bm3d2")
+    if x.shape[0] == 0:
+        return out
+    pilot = _lru(_plans, ("bm3d2 pilot",) + tuple(x.shape[:3]) + (x.device,), lambda: torch.empty_like(x), MAX_PLANS)
+    return bm3d_wiener(x, bm3d(x, sigma, search, group, out=pilot), sigma, search, group, out=out)

@@ -188,17 +188,18 @@ def ssim(a, b, max_val=None, scale=1.0, shift=0.0, out=None):
 
 SCORES = ("psnr_noisy", "psnr_denoised", "ssim_noisy", "ssim_denoised")
 BASELINE_SCORES = ("psnr_baseline", "ssim_baseline")
-BASELINES = ("median3", "nlm", "bm3d")
-_BASELINE_KEYS = {"nlm": ("h", "template", "search"), "bm3d": ("sigma", "search", "group")}
+BASELINES = ("median3", "nlm", "bm3d", "bm3d2")
+_BASELINE_KEYS = {"nlm": ("h", "template", "search"), "bm3d": ("sigma", "search", "group"),
+                  "bm3d2": ("sigma", "search", "group")}
 
 
 class Evaluator:
     """Scores a `Denoiser`'s frames against clean frames on the device: the noisy input and the
     denoised output stay where `Denoiser` holds them (uint8, dense), the clean frame is uploaded
     beside them, and only the 4 n scalars come back.  With a graph-capturing `Denoiser` the metrics
-    run eagerly on the same stream after the replay.  baseline "median3", "nlm" or "bm3d"
-    (baseline_args: the keywords of dgan.filters.nlm, h / template / search, or of dgan.filters.bm3d,
-    sigma / search / group) also puts the noisy input through
+    run eagerly on the same stream after the replay.  baseline "median3", "nlm", "bm3d" or "bm3d2"
+    (baseline_args: the keywords of dgan.filters.nlm, h / template / search, or of dgan.filters.bm3d
+    and bm3d2, sigma / search / group) also puts the noisy input through
     that classical filter on the device and scores it the same way: `psnr_baseline` and
     `ssim_baseline` join the result, 6 n scalars in all."""
 
@@ -218,7 +219,7 @@ class Evaluator:
         if baseline == "nlm":
             args = dict(zip(keys, filters.check_nlm(
                 args.get("h", 10), args.get("template", 7), args.get("search", 21), "baseline_args")))
-        if baseline == "bm3d":
+        if baseline in ("bm3d", "bm3d2"):
             args = dict(zip(keys, filters.check_bm3d(
                 args.get("sigma", 25), args.get("search", 21), args.get("group", 16), "baseline_args")))
         self.denoiser, self.baseline, self.baseline_args = denoiser, baseline, args

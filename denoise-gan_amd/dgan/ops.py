@@ -1528,3 +1528,16 @@ def bm3d(x, out, ws, sigma, search, group):
         raise DGError(f"bm3d workspace: expected a dense int32 vector of {2 * x.numel()} elements on {x.device}")
     call("dg_bm3d_u8", n, h, w, int(sigma), int(search), int(group), _p(x), _p(ws), ws.numel() * 4, _p(out), _stream())
     return out
+
+
+def bm3d_wiener(x, pilot, out, ws, sigma, search, group):
+    """out[n,h,w,3] = stage 2 of BM3D (dg_bm3d_wiener_u8) of the dense uint8 images x[n,h,w,3] with the
+    pilot estimate pilot[n,h,w,3]; out must be neither.  ws as in `bm3d`."""
+    n, h, w = _filter_pair(x, out, "bm3d_wiener")
+    _filter_pair(pilot, out, "bm3d_wiener pilot")
+    if (not isinstance(ws, torch.Tensor) or ws.dtype != torch.int32 or ws.dim() != 1 or not ws.is_contiguous()
+            or ws.device != x.device or ws.numel() < 2 * x.numel()):
+        raise DGError(f"bm3d_wiener workspace: expected a dense int32 vector of {2 * x.numel()} elements on {x.device}")
+    call("dg_bm3d_wiener_u8", n, h, w, int(sigma), int(search), int(group), _p(x), _p(pilot), _p(ws), ws.numel() * 4,
+         _p(out), _stream())
+    return out

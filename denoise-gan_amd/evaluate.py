@@ -16,7 +16,7 @@ the two directories are compared directly: psnr, ssim.  With --jpeg_quality Q in
 quality Q with 4:2:0 subsampling on the device (dgan.jpeg, the degradation the training pipeline
 applies, bit for bit what Pillow's codec returns), and the scores are the same.  The metrics are
 the tf.image.psnr / tf.image.ssim defaults on uint8 RGB (max_val 255), accumulated in fp64.
---baseline median3 | nlm | bm3d also puts every noisy image through that classical filter on the
+--baseline median3 | nlm | bm3d | bm3d2 also puts every noisy image through that classical filter on the
 device (dgan.filters; --nlm_h / --nlm_template / --nlm_search, --bm3d_sigma / --bm3d_search /
 --bm3d_group) and scores the result the same way:
 psnr_baseline, ssim_baseline, with and without --model.
@@ -42,8 +42,9 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
-parser.add_argument("--baseline", default=None, choices=["median3", "nlm", "bm3d"],
-                    help="Also score a classical filter of the noisy image: the 3x3 median, non-local means or BM3D.")
+parser.add_argument("--baseline", default=None, choices=["median3", "nlm", "bm3d", "bm3d2"],
+                    help="Also score a classical filter of the noisy image: the 3x3 median, non-local means, BM3D's "
+                         "first stage or both stages (bm3d2, which takes the --bm3d_* flags too).")
 parser.add_argument("--nlm_h", default=10, type=int, help="Non-local means: the filter strength (1..40).")
 parser.add_argument("--nlm_template", default=7, type=int, help="Non-local means: the patch size (3, 5 or 7).")
 parser.add_argument("--nlm_search", default=21, type=int, help="Non-local means: the search window (odd, 3..21).")
@@ -80,7 +81,7 @@ def _read_rgb(path):
 
 
 def baseline_args(args):
-    """The keywords of dgan.filters.nlm / bm3d that --baseline nlm / bm3d asks for ({} for the other
+    """The keywords of dgan.filters.nlm / bm3d / bm3d2 that --baseline nlm / bm3d / bm3d2 asks for ({} for the other
     baselines).  ValueError naming a bad --nlm_* / --bm3d_* value, or one given without its baseline.
     A namespace without the --bm3d_* attributes has their defaults."""
     from dgan.filters import check_bm3d, check_nlm
@@ -90,12 +91,12 @@ def baseline_args(args):
                                                     (getattr(args, "bm3d_group", None), 16)))
     if args.baseline != "nlm" and given != (10, 7, 21):
         raise ValueError("--nlm_h / --nlm_template / --nlm_search need --baseline nlm")
-    if args.baseline != "bm3d" and bm3d != (25, 21, 16):
-        raise ValueError("--bm3d_sigma / --bm3d_search / --bm3d_group need --baseline bm3d")
+    if args.baseline not in ("bm3d", "bm3d2") and bm3d != (25, 21, 16):
+        raise ValueError("--bm3d_sigma / --bm3d_search / --bm3d_group need --baseline bm3d or bm3d2")
     if args.baseline == "nlm":
         return dict(zip(("h", "template", "search"), check_nlm(*given, what="--baseline nlm")))
-    if args.baseline == "bm3d":
-        return dict(zip(("sigma", "search", "group"), check_bm3d(*bm3d, what="--baseline bm3d")))
+    if args.baseline in ("bm3d", "bm3d2"):
+        return dict(zip(("sigma", "search", "group"), check_bm3d(*bm3d, what=f"--baseline {args.baseline}")))
     return {}
 
 

@@ -820,6 +820,14 @@ int dg_bm3d_ws_bytes(int n, int h, int w, size_t *ws_bytes);
 int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in, void *ws,
                size_t ws_bytes, unsigned char *out, dg_stream_t stream);
 
+/* BM3D, stage 2 (dgan/filters.py bm3d_wiener_ref: block matching on `pilot`, an estimate of the clean
+ * frame such as stage 1's output, a Wiener weight per coefficient of the two groups' transforms,
+ * aggregation).  `in` is the noisy frame, `pilot` has its shape; both are only read and `out` must be
+ * neither.  Parameters, workspace and launches as dg_bm3d_u8; equal to the numpy reference bit for
+ * bit, and two calls give the same bits. */
+int dg_bm3d_wiener_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in,
+                      const unsigned char *pilot, void *ws, size_t ws_bytes, unsigned char *out, dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
