@@ -182,6 +182,7 @@ _SIGS = {
     "dg_bm3d_ws_bytes": (c_int, [c_int] * 3 + [ctypes.POINTER(c_size_t)]),
     "dg_bm3d_u8": (c_int, [c_int] * 6 + [_P, _P, c_size_t, _P, _P]),
     "dg_bm3d_wiener_u8": (c_int, [c_int] * 6 + [_P, _P, _P, c_size_t, _P, _P]),
+    "dg_dejpeg": (c_int, [c_int] * 3 + [_P, _P, c_void_p, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -29,12 +29,13 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + INCLUDE, "-I" + CSRC,
             "-Wno-unused-result"]
-# further flags of single sources; jpeg_enc.hip, jpeg_dec.hip, resize_pil.hip, png_enc.hip, bm3d.hip, bm3d_wiener.hip: integer
+# further flags of single sources; jpeg_enc.hip, jpeg_dec.hip, resize_pil.hip, png_enc.hip, bm3d.hip, bm3d_wiener.hip,
+# dejpeg.hip: integer
 # code, built without packed fp32 instructions
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"jpeg_enc.hip": _NO_PACKED_FP32, "jpeg_dec.hip": _NO_PACKED_FP32, "resize_pil.hip": _NO_PACKED_FP32,
                "png_enc.hip": _NO_PACKED_FP32, "bm3d.hip": _NO_PACKED_FP32,
-               "bm3d_wiener.hip": _NO_PACKED_FP32}
+               "bm3d_wiener.hip": _NO_PACKED_FP32, "dejpeg.hip": _NO_PACKED_FP32}
 
 
 def _sources():

@@ -24,6 +24,23 @@ post-filter (infer.py --post median3).
     bm3d_wiener  stage 2 (the collaborative Wiener filter) on a pilot estimate: `bm3d_wiener_ref`.
     bm3d2      both stages, stage 1's output as the pilot: `bm3d2_ref`.
 
+    dejpeg     JPEG artifact removal by shift-averaged re-application (Nosratinia 2001) with the
+               round trip of dgan.jpeg (4:2:0, quality Q in 1..100 or two tables t): for each of the
+               64 shifts (dy, dx) in 0..7 x 0..7
+                   s = the frame with its first row repeated dy times above and its first column dx
+                       times to the left, (h + dy) x (w + dx)
+                   r = roundtrip(s)[dy:, dx:], the round trip on the shifted frame's own geometry
+                       (its replication to multiples of 8, ch = ceil((h + dy) / 2), cw = ceil((w + dx)
+                       / 2), the bias by the shifted column's parity, the upsampler's clamps at
+                       ch - 1 / cw - 1, replication when cw <= 2)
+               and out = (sum of the 64 r + 32) >> 6.  The sum is at most 64 * 255: int32 holds
+               everything (`dejpeg_ref` takes the working type; tests/test_dejpeg.py holds int32 equal
+               to int64).
+
+`dejpeg` takes the quality (or the tables) the frame was coded with.  It is NOT a deblocker that
+estimates them from the pixels, and it is not claimed equal to any other implementation of
+re-application.
+
 `nlm` is the non-local means of Buades et al. with one weight for the three channels.  It is NOT
 claimed equal to cv2.fastNlMeansDenoisingColored, which filters in Lab with separate luminance and
 colour strengths and its own fixed-point weights.
@@ -31,7 +48,7 @@ colour strengths and its own fixed-point weights.
 `bm3d` is BM3D (Dabov et al.) with a Hadamard transform, a known cheap variant.  It is NOT the
 Bior / DCT profile of the original paper and is not claimed equal to any other implementation.
 
-`median3_ref` / `nlm_table` / `nlm_ref` / `bm3d_ref` / `bm3d_wiener_ref` / `bm3d2_ref` are pure numpy and import neither torch nor the library.
+`median3_ref` / `nlm_table` / `nlm_ref` / `bm3d_ref` / `bm3d_wiener_ref` / `bm3d2_ref` / `dejpeg_ref` are pure numpy and import neither torch nor the library.
 """
 import math
 
@@ -351,6 +368,38 @@ def bm3d2_ref(img_u8, sigma=25, search=21, group=16, dtype=np.int64):
 
 
 # ---------------------------------------------------------------------------
+# JPEG artifact removal: shift-averaged re-application
+# ---------------------------------------------------------------------------
+def check_dejpeg(quality, tables, what="dejpeg"):
+    """The uint8 [2,64] tables of a call: `tables` checked, or those of `quality`; ValueError naming
+    the bad argument."""
+    from .jpeg import _check_quality, quant_tables
+    quality = _check_quality(quality, what)
+    if tables is None:
+        return quant_tables(quality)
+    t = np.asarray(tables)
+    if t.dtype != np.uint8 or t.shape != (2, 64) or int(t.min()) < 1:
+        raise ValueError(f"{what}: tables must be uint8 [2,64] with entries >= 1, got {t.dtype} {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def dejpeg_ref(img_u8, quality=50, tables=None, dtype=np.int64):
+    """The definition on the host: uint8 [n,h,w,3] or [h,w,3] -> the same shape and dtype (module
+    docstring).  tables: uint8 [2,64], row-major, entries >= 1, in place of quant_tables(quality)
+    (a file's own: jpeg_parse(data).quant).  dtype: the working integer type, np.int64 or np.int32."""
+    from .jpeg import _roundtrip
+    a, single = _images(img_u8, "dejpeg_ref", dtype)
+    tables = check_dejpeg(quality, tables, "dejpeg_ref")
+    acc = np.zeros(a.shape, dtype)
+    for dy in range(8):
+        for dx in range(8):
+            s = np.pad(a, ((0, 0), (dy, 0), (dx, 0), (0, 0)), mode="edge")
+            acc += _roundtrip(s, tables, dtype)[:, dy:, dx:]
+    out = ((acc + 32) >> 6).astype(np.uint8)
+    return out[0] if single else out
+
+
+# ---------------------------------------------------------------------------
 # device code below: torch and the library are imported on use
 # ---------------------------------------------------------------------------
 MAX_PLANS = 8   # plans kept over all filters, least recently used first out (metrics._lru)
@@ -476,3 +525,15 @@ def bm3d2(x, sigma=25, search=21, group=16, out=None):
         return out
     pilot = _lru(_plans, ("bm3d2 pilot",) + tuple(x.shape[:3]) + (x.device,), lambda: torch.empty_like(x), MAX_PLANS)
     return bm3d_wiener(x, bm3d(x, sigma, search, group, out=pilot), sigma, search, group, out=out)
+
+
+def dejpeg(x, quality=50, tables=None, out=None):
+    """A dense uint8 NHWC device tensor [n,h,w,3] -> its shift-averaged re-application at `quality`
+    (or with the uint8 [2,64] `tables`), equal to `dejpeg_ref` bit for bit.  `out` as in `median3`.
+    One launch, no workspace; the 128 table bytes ride in the kernel's arguments, so there is no
+    device table to upload or keep: a repeated call allocates nothing, does no host sync and can be
+    captured in a graph."""
+    from . import ops
+    tables = check_dejpeg(quality, tables)
+    out = _device_pair(x, out, "dejpeg")
+    return ops.dejpeg(x, out, tables) if x.shape[0] else out

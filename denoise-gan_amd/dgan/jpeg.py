@@ -196,12 +196,17 @@ def jpeg_ref(img_u8, quality, dtype=np.int64):
         raise ValueError(f"jpeg_ref: dtype must be np.int64 or np.int32, got {dtype!r}")
     tables = quant_tables(_check_quality(quality, "jpeg_ref"))
     single = a.ndim == 3
-    if single:
-        a = a[None]
-    n, h, w = a.shape[:3]
-    Y, Cb, Cr = _planes(a, dtype)
-    out = _pixels(_codec(Y, tables[0]), _codec(Cb, tables[1]), _codec(Cr, tables[1]), h, w)
+    out = _roundtrip(a[None] if single else a, tables, dtype)
     return out[0] if single else out
+
+
+def _roundtrip(a, tables, dtype):
+    """uint8 [n,h,w,3] through the round trip with the uint8 [2,64] tables (luminance, chrominance),
+    in the working type `dtype`: `jpeg_ref` with the tables of its quality, and dgan.filters.dejpeg_ref
+    with any."""
+    h, w = a.shape[1:3]
+    Y, Cb, Cr = _planes(a, dtype)
+    return _pixels(_codec(Y, tables[0]), _codec(Cb, tables[1]), _codec(Cr, tables[1]), h, w)
 
 
 def _pixels(Y, Cb, Cr, h, w):

@@ -188,18 +188,19 @@ def ssim(a, b, max_val=None, scale=1.0, shift=0.0, out=None):
 
 SCORES = ("psnr_noisy", "psnr_denoised", "ssim_noisy", "ssim_denoised")
 BASELINE_SCORES = ("psnr_baseline", "ssim_baseline")
-BASELINES = ("median3", "nlm", "bm3d", "bm3d2")
+BASELINES = ("median3", "nlm", "bm3d", "bm3d2", "dejpeg")
 _BASELINE_KEYS = {"nlm": ("h", "template", "search"), "bm3d": ("sigma", "search", "group"),
-                  "bm3d2": ("sigma", "search", "group")}
+                  "bm3d2": ("sigma", "search", "group"), "dejpeg": ("quality",)}
 
 
 class Evaluator:
     """Scores a `Denoiser`'s frames against clean frames on the device: the noisy input and the
     denoised output stay where `Denoiser` holds them (uint8, dense), the clean frame is uploaded
     beside them, and only the 4 n scalars come back.  With a graph-capturing `Denoiser` the metrics
-    run eagerly on the same stream after the replay.  baseline "median3", "nlm", "bm3d" or "bm3d2"
-    (baseline_args: the keywords of dgan.filters.nlm, h / template / search, or of dgan.filters.bm3d
-    and bm3d2, sigma / search / group) also puts the noisy input through
+    run eagerly on the same stream after the replay.  baseline "median3", "nlm", "bm3d", "bm3d2" or
+    "dejpeg" (baseline_args: the keywords of dgan.filters.nlm, h / template / search, of dgan.filters.bm3d
+    and bm3d2, sigma / search / group, or of dgan.filters.dejpeg, quality: when it is not given,
+    `evaluate_degraded` uses the quality it degrades with and `evaluate` 50) also puts the noisy input through
     that classical filter on the device and scores it the same way: `psnr_baseline` and
     `ssim_baseline` join the result, 6 n scalars in all."""
 
@@ -222,6 +223,8 @@ class Evaluator:
         if baseline in ("bm3d", "bm3d2"):
             args = dict(zip(keys, filters.check_bm3d(
                 args.get("sigma", 25), args.get("search", 21), args.get("group", 16), "baseline_args")))
+        if baseline == "dejpeg" and "quality" in args:
+            filters.check_dejpeg(args["quality"], None, "baseline_args")
         self.denoiser, self.baseline, self.baseline_args = denoiser, baseline, args
         self.scores = SCORES + (BASELINE_SCORES if baseline else ())
         self._bufs = {}
@@ -237,11 +240,14 @@ class Evaluator:
                              torch.empty((len(self.scores), shape[0]), dtype=torch.float64, device=dev)),
                     self.MAX_SHAPES)
 
-    def filtered(self, f):
-        """The frame's noisy input through the baseline filter: the filter's own buffer of that shape."""
+    def filtered(self, f, quality=50):
+        """The frame's noisy input through the baseline filter: the filter's own buffer of that shape.
+        quality: what "dejpeg" takes when baseline_args names none."""
         from . import filters
         if self.baseline == "median3":
             return filters.median3(f.u8_in)
+        if self.baseline == "dejpeg":
+            return filters.dejpeg(f.u8_in, self.baseline_args.get("quality", quality))
         return getattr(filters, self.baseline)(f.u8_in, **self.baseline_args)
 
     def evaluate(self, noisy_u8, clean_u8):
@@ -263,13 +269,13 @@ class Evaluator:
         ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))
         return self._score(f, ref, res)
 
-    def _score(self, f, ref, res):
+    def _score(self, f, ref, res, quality=50):
         psnr(f.u8_in, ref, out=res[0])
         psnr(f.u8_out, ref, out=res[1])
         ssim(f.u8_in, ref, out=res[2])
         ssim(f.u8_out, ref, out=res[3])
         if self.baseline:
-            base = self.filtered(f)
+            base = self.filtered(f, quality)
             psnr(base, ref, out=res[4])
             ssim(base, ref, out=res[5])
         r = res.cpu().numpy()
@@ -295,7 +301,7 @@ class Evaluator:
         ref.copy_(torch.from_numpy(np.ascontiguousarray(clean)))
         jpeg_roundtrip(ref, quality, out=f.u8_in)
         self.denoiser.run_frame(f)
-        return self._score(f, ref, res)
+        return self._score(f, ref, res, quality)
 
 
 SR_SCORES = ("psnr_bicubic", "psnr_upscaled", "ssim_bicubic", "ssim_upscaled")

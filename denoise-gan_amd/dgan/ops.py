@@ -1541,3 +1541,16 @@ def bm3d_wiener(x, pilot, out, ws, sigma, search, group):
     call("dg_bm3d_wiener_u8", n, h, w, int(sigma), int(search), int(group), _p(x), _p(pilot), _p(ws), ws.numel() * 4,
          _p(out), _stream())
     return out
+
+
+def dejpeg(x, out, qtab):
+    """out[n,h,w,3] = the shift-averaged re-application (dg_dejpeg) of the dense uint8 images
+    x[n,h,w,3]; out must not be x.  qtab: the host uint8 [2,64] tables (dgan.jpeg.quant_tables, or a
+    file's own)."""
+    n, h, w = _filter_pair(x, out, "dejpeg")
+    q = np.asarray(qtab)
+    if q.dtype != np.uint8 or q.shape != (2, 64) or int(q.min()) < 1:
+        raise DGError(f"dejpeg: qtab must be uint8 [2,64] with entries >= 1, got {q.dtype} {q.shape}")
+    tables = (ctypes.c_ubyte * 128).from_buffer_copy(np.ascontiguousarray(q).tobytes())
+    call("dg_dejpeg", n, h, w, _p(x), _p(out), tables, _stream())
+    return out

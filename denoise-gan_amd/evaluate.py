@@ -16,9 +16,10 @@ the two directories are compared directly: psnr, ssim.  With --jpeg_quality Q in
 quality Q with 4:2:0 subsampling on the device (dgan.jpeg, the degradation the training pipeline
 applies, bit for bit what Pillow's codec returns), and the scores are the same.  The metrics are
 the tf.image.psnr / tf.image.ssim defaults on uint8 RGB (max_val 255), accumulated in fp64.
---baseline median3 | nlm | bm3d | bm3d2 also puts every noisy image through that classical filter on the
+--baseline median3 | nlm | bm3d | bm3d2 | dejpeg also puts every noisy image through that classical filter on the
 device (dgan.filters; --nlm_h / --nlm_template / --nlm_search, --bm3d_sigma / --bm3d_search /
---bm3d_group) and scores the result the same way:
+--bm3d_group, --dejpeg_quality, which defaults to --jpeg_quality when that is given and to 50
+otherwise) and scores the result the same way:
 psnr_baseline, ssim_baseline, with and without --model.
 """
 import json
@@ -42,15 +43,18 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
-parser.add_argument("--baseline", default=None, choices=["median3", "nlm", "bm3d", "bm3d2"],
+parser.add_argument("--baseline", default=None, choices=["median3", "nlm", "bm3d", "bm3d2", "dejpeg"],
                     help="Also score a classical filter of the noisy image: the 3x3 median, non-local means, BM3D's "
-                         "first stage or both stages (bm3d2, which takes the --bm3d_* flags too).")
+                         "first stage or both stages (bm3d2, which takes the --bm3d_* flags too), or JPEG artifact "
+                         "removal by shift-averaged re-application (dejpeg).")
 parser.add_argument("--nlm_h", default=10, type=int, help="Non-local means: the filter strength (1..40).")
 parser.add_argument("--nlm_template", default=7, type=int, help="Non-local means: the patch size (3, 5 or 7).")
 parser.add_argument("--nlm_search", default=21, type=int, help="Non-local means: the search window (odd, 3..21).")
 parser.add_argument("--bm3d_sigma", default=25, type=int, help="BM3D: the noise level it is set for (1..40).")
 parser.add_argument("--bm3d_search", default=21, type=int, help="BM3D: the search window (odd, 3..21).")
 parser.add_argument("--bm3d_group", default=16, type=int, help="BM3D: the most patches of a group (2, 4, 8 or 16).")
+parser.add_argument("--dejpeg_quality", default=None, type=int,
+                    help="dejpeg: the quality the noisy images were coded with (1..100; default: --jpeg_quality, else 50).")
 parser.add_argument("--json", default=None, type=str, help="Also write the scores and their means to this file.")
 
 
@@ -84,7 +88,7 @@ def baseline_args(args):
     """The keywords of dgan.filters.nlm / bm3d / bm3d2 that --baseline nlm / bm3d / bm3d2 asks for ({} for the other
     baselines).  ValueError naming a bad --nlm_* / --bm3d_* value, or one given without its baseline.
     A namespace without the --bm3d_* attributes has their defaults."""
-    from dgan.filters import check_bm3d, check_nlm
+    from dgan.filters import check_bm3d, check_dejpeg, check_nlm
     given = (args.nlm_h, args.nlm_template, args.nlm_search)
     bm3d = tuple(d if v is None else v for v, d in ((getattr(args, "bm3d_sigma", None), 25),
                                                     (getattr(args, "bm3d_search", None), 21),
@@ -93,6 +97,13 @@ def baseline_args(args):
         raise ValueError("--nlm_h / --nlm_template / --nlm_search need --baseline nlm")
     if args.baseline not in ("bm3d", "bm3d2") and bm3d != (25, 21, 16):
         raise ValueError("--bm3d_sigma / --bm3d_search / --bm3d_group need --baseline bm3d or bm3d2")
+    quality = getattr(args, "dejpeg_quality", None)
+    if args.baseline != "dejpeg" and quality is not None:
+        raise ValueError("--dejpeg_quality needs --baseline dejpeg")
+    if args.baseline == "dejpeg":
+        quality = next((q for q in (quality, getattr(args, "jpeg_quality", None)) if q is not None), 50)
+        check_dejpeg(quality, None, "--baseline dejpeg")
+        return {"quality": int(quality)}
     if args.baseline == "nlm":
         return dict(zip(("h", "template", "search"), check_nlm(*given, what="--baseline nlm")))
     if args.baseline in ("bm3d", "bm3d2"):

@@ -10,7 +10,8 @@ with --margin M runs T x T tiles with M pixels of context instead, --batch of th
 --post median3 puts the denoised frame through a 3x3 median on the device before it is read back
 (dgan.filters.median3: the reference's `sr_denoise` output, unit_test.py:95); --post bm3d through
 BM3D's first stage set for --bm3d_sigma (dgan.filters.bm3d), --post bm3d2 through both stages
-(dgan.filters.bm3d2).  --format jpg writes
+(dgan.filters.bm3d2), --post dejpeg through the shift-averaged JPEG re-application at
+--dejpeg_quality (dgan.filters.dejpeg).  --format jpg writes
 <stem>.jpg at --jpeg_quality instead: the frame is encoded on the device (dgan.jpeg.jpeg_encode) and
 only the file's bytes are read back; --format png writes <stem>.png the same way, lossless
 (dgan.png.png_encode).  --decode device reads baseline 4:2:0 .jpg / .jpeg inputs as bytes
@@ -35,9 +36,11 @@ parser.add_argument("--tile", default=0, type=int, help="Tile size, a multiple o
 parser.add_argument("--margin", default=0, type=int, help="Context pixels on each side of a tile.")
 parser.add_argument("--pad", default="black", choices=["black", "reflect"], help="Values outside the image.")
 parser.add_argument("--batch", default=8, type=int, help="Tiles per forward.")
-parser.add_argument("--post", default=None, choices=["median3", "bm3d", "bm3d2"],
+parser.add_argument("--post", default=None, choices=["median3", "bm3d", "bm3d2", "dejpeg"],
                     help="A classical filter applied to the denoised image on the device (default: none).")
 parser.add_argument("--bm3d_sigma", default=25, type=int, help="The noise level --post bm3d / bm3d2 is set for (1..40).")
+parser.add_argument("--dejpeg_quality", default=50, type=int,
+                    help="The JPEG quality --post dejpeg re-applies (1..100).")
 parser.add_argument("--format", default="keep", choices=["keep", "jpg", "png"],
                     help="keep: Pillow writes every image under its own name; jpg / png: baseline JPEG or PNG files "
                          "encoded on the device.")
@@ -114,6 +117,9 @@ def post_filtered(frame, args):
     if args.post == "bm3d2":
         from dgan.filters import bm3d2
         return bm3d2(frame.contiguous(), args.bm3d_sigma)
+    if args.post == "dejpeg":
+        from dgan.filters import dejpeg
+        return dejpeg(frame.contiguous(), args.dejpeg_quality)
     return frame
 
 

@@ -828,6 +828,17 @@ int dg_bm3d_u8(int n, int h, int w, int sigma, int search, int group, const unsi
 int dg_bm3d_wiener_u8(int n, int h, int w, int sigma, int search, int group, const unsigned char *in,
                       const unsigned char *pilot, void *ws, size_t ws_bytes, unsigned char *out, dg_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * JPEG artifact removal (dgan/filters.py dejpeg_ref): shift-averaged re-application of the 4:2:0
+ * round trip above.  Dense RGB images [n][h][w][3] -> the same shape, any byte alignment: the frame
+ * shifted by each (dy, dx) in 0..7 x 0..7 (first row / column replicated), through the round trip
+ * with `qtab` on the shifted frame's own geometry, shifted back; out = (the sum of the 64 + 32) >> 6.
+ * qtab: 128 HOST bytes, the luminance then the chrominance table, row-major, every entry >= 1.
+ * One launch, no workspace, integer arithmetic only: equal to the numpy reference bit for bit.
+ * `out` must not be `in`. */
+int dg_dejpeg(int n, int h, int w, const unsigned char *in, unsigned char *out, const unsigned char *qtab,
+              dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
